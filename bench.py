@@ -1,6 +1,20 @@
 """Headline benchmark: prove time + trace rows/s of the 3x3 permutation AIR.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 19] [--ncols 3]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it sets up,
+warms up, times the K steps, writes ``--dump-outputs`` and prints the line
+(``value``, ``ms_per_step`` and the workload's description).  ``--full`` adds
+everything else listed under "Legs" below: the extra legs, the CPU baseline,
+the roofline objects, the phase breakdown, the verifier's check of the last
+proof and the machine-speed stamp.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its
+caller, the serialized proof, as ``DIR/proof.npy`` (rank 0's; float32, one
+element per proof byte, so exact).  The trace and the transcript are seeded,
+so the same arguments give the same proof from run to run and two builds can
+be compared output for output.
 
 A "step" is one full ``p3_uni_stark::prove`` (bin/src/main.rs:80-86) of the
 3x3 permutation AIR (3 'from' + 3 'to' columns + b_inverse + check, w = 8,
@@ -14,7 +28,7 @@ without a launcher, bench.py starts ``torch.distributed.run --nproc-per-node
 N`` itself as a child process (before anything touches the GPU) and exits with
 its status.  WORLD_SIZE != --gpus is an error, never a silent single rank.
 
-Legs (rank 0 prints ONE JSON line):
+Legs (rank 0 prints ONE JSON line; all but `value` need --full):
   value          C5 replicas: every rank proves its own
                  independent 2^log_n trace, no data-path collective; value =
                  all rows / max-over-ranks wall time ("scaling": "weak").
@@ -218,6 +232,14 @@ def parse(argv=None):
                     help="perm: the 3x3 permutation AIR (headline); wide: SURVEY 8(d) C3 synthetic "
                          "wide AIR (4 LogUp lookups + 8 permutation groups of 6+6, W = 184)")
     ap.add_argument("--seed", type=int, default=0x4C494E4541)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the extra legs (batch, wide_c3, shape_bench_log, sharded, inflight, "
+                         "host trace), the CPU baseline, the roofline objects, the phase breakdown, the verifier's "
+                         "check of the last proof and the machine-speed stamp; the options below that shape or skip "
+                         "these only matter with it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes the last timed step's result, the serialized proof, "
+                         "to DIR/proof.npy (float32, one element per byte)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-log-n", type=int, default=None,
                     help="CPU-baseline size (rows = 2^cpu_log_n; default: the headline's --log-n, BASELINE.md's "
@@ -269,7 +291,10 @@ def parse(argv=None):
                          "reported as the separate 'inflight' field, never as value); 0 or 1 disables")
     ap.add_argument("--dry-run", action="store_true",
                     help="set up the ranks and the control group, print the rank census, no GPU work")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _free_port() -> int:
@@ -311,10 +336,16 @@ def main():
         dist.close()
         return 0
 
-    shard_sizes = shard_leg_sizes(args, world)
+    shard_sizes = shard_leg_sizes(args, world) if args.full else []
     if args.shard or (shard_sizes and world > 1):
         from linea_stark_prover_amd import shard as S  # noqa: F401  (torch before the HIP library)
     out, ctx = main_leg(args, dist, ranks_seen)
+    if not args.full:  # a plain run: the headline line and nothing else
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        ctx.close()
+        dist.close()
+        return 0
     batch_sizes = [] if args.batch_leg == "none" or args.shard or args.air != "perm" else \
         [int(x) for x in args.batch_leg.split(",") if x]
     if batch_sizes:
@@ -360,6 +391,22 @@ def device_of(args, dist) -> int:
     return dist.local_rank % max(n.value, 1)
 
 
+DUMP_MAX_ELEMS = 16 << 20  # 64 MB of float32
+
+
+def dump_outputs(path, proof: bytes):
+    """--dump-outputs: what the timed path handed its caller in the last timed
+    step -- the serialized proof -- as `path`/proof.npy, float32, one element
+    per byte (exact).  A proof of more than DUMP_MAX_ELEMS bytes (none of the
+    sizes here comes near) is written as a fixed, seeded sample of its bytes."""
+    import numpy as np
+    a = np.frombuffer(proof, dtype=np.uint8)
+    if a.size > DUMP_MAX_ELEMS:
+        a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "proof.npy"), a.astype(np.float32))
+
+
 def main_leg(args, dist, ranks_seen):
     from linea_stark_prover_amd.air import permutation_air
     from linea_stark_prover_amd.prover import Context, StarkConfig, gen_permutation_trace, gen_wide_trace
@@ -372,7 +419,9 @@ def main_leg(args, dist, ranks_seen):
     ctx = Context(cfg, device=device_of(args, dist))
     # timed proofs record device events only for the phases the roofline
     # objects read; the full phase breakdown comes from one extra proof after
-    # the timed steps (every phase event costs host API time inside the step)
+    # the timed steps (every phase event costs host API time inside the step).
+    # A plain run reads none of them but keeps the same setting, so that its
+    # step is the step --full times.
     ctx.set_phase_timing(True, only=ROOFLINE_PHASES)
     if shard:
         from linea_stark_prover_amd import shard as S
@@ -404,28 +453,33 @@ def main_leg(args, dist, ranks_seen):
         step = lambda: S.prove_sharded(ctx, dtrace, air, pub, h, w)  # noqa: E731
     else:
         step = lambda: ctx.prove(dtrace, air, pub, h, w)  # noqa: E731
-    clocks = ClockSampler(ctx.device)
+    full = args.full
+    # the engine clock is sampled only for --full's machine-speed stamp
+    clocks = ClockSampler(ctx.device) if full else None
     elapsed, proof = timed_steps(step, args.steps, args.warmup, dist, sync=ctx.synchronize, step_times=step_s,
-                                 on_start=clocks.start)
-    sclk = clocks.stop()
-    # the last timed step's LDE and Merkle times (HIP events on the prover's
-    # stream, inside the timed region): the library resolves its phase events
-    # lazily, so reading them after every step would put that inside the timing
-    record()
-    roof_phases = dict(phases_acc)
-    # every phase, from one more (untimed) proof
-    ctx.set_phase_timing(True)
-    step()
-    phases_acc.clear()
-    record()
-    phases = dict(phases_acc)
-    ctx.set_phase_timing(True, only=ROOFLINE_PHASES)
-    verified = ctx.verify(proof, air, pub) if proof is not None else False
+                                 on_start=clocks.start if full else lambda: None)
+    if rank == 0 and args.dump_outputs and proof is not None:
+        dump_outputs(args.dump_outputs, proof)
     if rank == 0 and args.dump_proof and proof is not None:
         with open(args.dump_proof, "wb") as f:
             f.write(proof)
+    if full:
+        sclk = clocks.stop()
+        # the last timed step's LDE and Merkle times (HIP events on the prover's
+        # stream, inside the timed region): the library resolves its phase events
+        # lazily, so reading them after every step would put that inside the timing
+        record()
+        roof_phases = dict(phases_acc)
+        # every phase, from one more (untimed) proof
+        ctx.set_phase_timing(True)
+        step()
+        phases_acc.clear()
+        record()
+        phases = dict(phases_acc)
+        ctx.set_phase_timing(True, only=ROOFLINE_PHASES)
+        verified = ctx.verify(proof, air, pub) if proof is not None else False
     # one process per rank: every collective of the last proof, per rank (lsp_comm_log)
-    table = collective_table(ctx, dist) if shard and world > 1 else None
+    table = collective_table(ctx, dist) if full and shard and world > 1 else None
     comm = getattr(ctx, "_comm", None)
     if args.dump_comm_schedule and comm is not None:
         with open(f"{args.dump_comm_schedule}.{rank}.json", "w") as f:
@@ -435,18 +489,7 @@ def main_leg(args, dist, ranks_seen):
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = (1 if shard else world) * h * args.steps / elapsed
-        N = h << cfg.log_blowup
         q = 1 << air_log_q(air, cfg)
-        lde_ms = roof_phases.get("coset_lde_batch", float("nan"))
-        Nr = N // world if shard else N  # LDE rows (Merkle leaves) this rank computes
-        lde_bytes = 32 * w * (h + Nr)
-        achieved = lde_bytes / (lde_ms * 1e-3) / 1e9
-        lde_frmul = lde_products(h, w, Nr // h)
-        frmul_gps = lde_frmul / (lde_ms * 1e-3) / 1e9
-        merkle_ms = roof_phases.get("merkle tree", float("nan"))
-        trace_perms = Nr * ((w + 1) // 2) + (Nr - 1)
-        valu_achieved = trace_perms / (merkle_ms * 1e-3) / 1e6
-        peak = valu_peak()
         out = {
             "metric": METRIC,
             "value": value,
@@ -472,12 +515,27 @@ def main_leg(args, dist, ranks_seen):
                        "log_n": args.log_n, "width": w, "fri_queries": cfg.num_queries,
                        "parallelism": (f"sharded{world} ({args.comm})" if shard else
                                        f"replicas{world}" if world > 1 else "single-gpu")},
+            "lib_src_sha16": LIB_SRC,
+            "host_threads": ctx.host_threads(),
+            "full": full,
+        }
+    if rank == 0 and full:
+        N = h << cfg.log_blowup
+        lde_ms = roof_phases.get("coset_lde_batch", float("nan"))
+        Nr = N // world if shard else N  # LDE rows (Merkle leaves) this rank computes
+        lde_bytes = 32 * w * (h + Nr)
+        achieved = lde_bytes / (lde_ms * 1e-3) / 1e9
+        lde_frmul = lde_products(h, w, Nr // h)
+        frmul_gps = lde_frmul / (lde_ms * 1e-3) / 1e9
+        merkle_ms = roof_phases.get("merkle tree", float("nan"))
+        trace_perms = Nr * ((w + 1) // 2) + (Nr - 1)
+        valu_achieved = trace_perms / (merkle_ms * 1e-3) / 1e6
+        peak = valu_peak()
+        out.update({
             "verified": bool(verified),
             "phases_ms": {k: round(v, 3) for k, v in phases.items()},
             "phases_source": "one untimed proof after the timed steps; the timed steps time only "
                              + " and ".join(ROOFLINE_PHASES) + " (the roofline objects' ms)",
-            "lib_src_sha16": LIB_SRC,
-            "host_threads": ctx.host_threads(),
             "roofline": {"bound": "hbm", "kernel": "coset_lde_batch (trace, w x 2^log_n -> 8x)",
                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": lde_traffic(args.log_n, w),
@@ -526,7 +584,7 @@ def main_leg(args, dist, ranks_seen):
                               "valu_issue": valu_issue(["k_hash_rows1<11u, 1>", "k_merkle_level<11u, 1>"]),
                               "valu_issue_source": VALU_SRC.get("src"),
                               "perms": trace_perms, "fr_mul_per_perm": FR_MUL_PER_PERM, "ms": merkle_ms},
-        }
+        })
         out["box_speed"] = box_speed(ctx, sclk, clocks.status, ms_per_step)
         if table is not None:
             out.update(table)

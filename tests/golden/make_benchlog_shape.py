@@ -2,7 +2,7 @@
 of one proof's structure: the 6+6 permutation AIR, w = 14, at 2^19 rows) into
 tests/golden/benchlog_shape.json.
 
-    python tests/golden/make_benchlog_shape.py /root/reference/bench.log
+    python tests/golden/make_benchlog_shape.py <reference checkout>/bench.log
 
 Output: the span names with their `dims:` / `added_bits:` annotations, in log
 order (timings dropped) -- data the reference already holds, read as text.
@@ -12,7 +12,9 @@ import os
 import re
 import sys
 
-src = sys.argv[1] if len(sys.argv) > 1 else "/root/reference/bench.log"
+if len(sys.argv) != 2:
+    sys.exit(__doc__)
+src = sys.argv[1]
 out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "benchlog_shape.json")
 spans = []
 for ln, line in enumerate(open(src, encoding="utf-8"), 1):

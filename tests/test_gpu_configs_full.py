@@ -94,7 +94,7 @@ def test_configs4_two_replica_ranks_at_2e22(gpu_ctx, tmp_path):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
            "127.0.0.1", "--master-port", "29631", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device", "0",
-           "--log-n", "10", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--shard-leg", "none",
+           "--log-n", "10", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--shard-leg", "none",
            "--batch-leg", "22", "--batch-leg-steps", "1", "--dump-batch-proofs", str(prefix)]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

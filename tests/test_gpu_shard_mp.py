@@ -22,7 +22,8 @@ def _run(tmp_path, nproc, comm, port, log_n=10, schedules=None, env_extra=None, 
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", str(nproc), "--shard", "--comm", comm, "--device", "0", "--log-n", str(log_n), "--steps", "1",
-           "--warmup", "0", "--no-cpu-baseline", "--dump-proof", str(out), "--dump-comm-schedule", str(sched)]
+           "--warmup", "0", "--full", "--no-cpu-baseline", "--dump-proof", str(out), "--dump-comm-schedule",
+           str(sched)]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     if nproc > 1:  # the per-collective table of the JSON line (lsp_comm_log on every rank)
@@ -115,13 +116,13 @@ def test_rccl_transport_single_rank(gpu_ctx, tmp_path):
     assert _run(tmp_path, 1, "rccl", 29613) == _single(gpu_ctx)
 
 
-def _bench_json(args, timeout=420):
+def _bench_json(args, timeout=420, full=True):
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, capture_output=True,
-                       text=True, timeout=timeout, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + (["--full"] if full else []) + args,
+                       env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
     assert len(lines) == 1, r.stdout[-3000:]
@@ -166,3 +167,21 @@ def test_bench_sharded_leg_single_gpu_equals_prove():
     assert sh["comm"] == "solo" and sh["n_ranks_seen"] == 1
     assert sh["runs"][0]["verified"] is True
     assert o["prove_time_host_trace_s"]["median"] > 0
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_proof(gpu_ctx, tmp_path):
+    """without --full the line is the headline alone (no leg, baseline, roofline
+    or check of its own), --steps sets the number of timed steps, and
+    --dump-outputs writes the last timed step's proof: the seeded inputs make it
+    the single-context proof, byte for byte"""
+    o = _bench_json(["--log-n", "10", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")],
+                    full=False)
+    assert o["full"] is False and o["steps"] == 3 and o["warmup"] == 1 and o["n_gpus"] == 1
+    assert o["unit"] == "trace-rows/s" and o["higher_is_better"] is True and o["dtype"].startswith("fr253")
+    assert o["ms_per_step"] > 0 and o["value"] == pytest.approx((1 << 10) / (o["ms_per_step"] * 1e-3))
+    moved = {"verified", "phases_ms", "roofline", "roofline_valu", "box_speed", "inflight", "prove_time_host_trace_s",
+             "batch", "wide_c3", "shape_bench_log", "sharded", "cpu_baseline"}
+    assert not moved & set(o), moved & set(o)
+    got = np.load(tmp_path / "dump" / "proof.npy")
+    assert got.dtype == np.float32 and sorted(p.name for p in (tmp_path / "dump").iterdir()) == ["proof.npy"]
+    assert got.astype(np.uint8).tobytes() == _single(gpu_ctx)

@@ -139,6 +139,24 @@ def test_bench_helpers():
     assert bench.TRAFFIC_SRC[(5, 3)].startswith("null")
 
 
+def test_bench_full_is_off_by_default_and_dump_outputs_is_exact(tmp_path):
+    """--full is off unless given; --dump-outputs writes the proof's bytes as
+    float32, one element per byte, which reads back exactly"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"]).full is False
+    args = bench.parse(["--steps", "7", "--full", "--dump-outputs", str(tmp_path / "d")])
+    assert args.full is True and args.steps == 7 and args.dump_outputs == str(tmp_path / "d")
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    proof = bytes(range(256)) * 3
+    bench.dump_outputs(args.dump_outputs, proof)
+    got = np.load(tmp_path / "d" / "proof.npy")
+    assert got.dtype == np.float32 and got.shape == (len(proof),)
+    assert got.astype(np.uint8).tobytes() == proof
+
+
 def test_host_pool_split_follows_affinity(tmp_path, product_lib):
     """init_from_env sizes each rank's host pool from the ranks that share its
     CPU set: ranks pinned to disjoint sets keep their own (no division), ranks
