@@ -44,7 +44,8 @@ enum {
     LSP_E_HIP = 3,     /* HIP runtime error */
     LSP_E_SIZE = 4,    /* height not a power of two / too large */
     LSP_E_VERIFY = 5,  /* proof rejected */
-    LSP_E_STATE = 6    /* no GPU / context unusable */
+    LSP_E_STATE = 6,   /* no GPU / context unusable */
+    LSP_E_CONSTRAINT = 7 /* trace violates the AIR (only from the opt-in check inside the prove call) */
 };
 
 enum { LSP_MEM_HOST = 0, LSP_MEM_DEVICE = 1 };
@@ -238,6 +239,61 @@ int lsp_log_quotient_degree(const int32_t *air, size_t air_len, int32_t public_d
  * (air/src/lib.rs:47-167): out[i], i < h << log_q, natural order on GEN*H_Q. */
 int lsp_quotient_values(lsp_ctx *ctx, const lsp_fr *lde, size_t h, size_t w, const int32_t *air, size_t air_len,
                         const lsp_fr *public_values, size_t npub, const lsp_fr *alpha, lsp_fr *out, int mem);
+
+/* ----------------------------------------------------- check_constraints */
+/* p3_uni_stark::check_constraints [EXT p3-uni-stark check_constraints.rs],
+ * which the reference's debug build runs inside p3_uni_stark::prove
+ * (bin/src/main.rs:80-86, #[cfg(debug_assertions)]): LineaAIR::eval
+ * (air/src/lib.rs:47-167) on every pair of adjacent rows of the trace itself
+ * (natural order, no LDE), local = row i, next = row (i + 1) mod h, with the
+ * 0/1 selectors is_first_row = (i == 0), is_last_row = (i == h - 1),
+ * is_transition = (i != h - 1); a constraint whose selector is 0 is satisfied.
+ * Constraints are numbered in eval's order, the order of the quotient's fold. */
+enum {
+    LSP_CONSTRAINT_B_INVERSE = 0, /* b_chal * b_inverse - 1 (lookup: one per table) */
+    LSP_CONSTRAINT_A_INVERSE = 1, /* lookup: a_chal * a_inverses - 1 */
+    LSP_CONSTRAINT_FIRST_ROW = 2, /* when_first_row: the check column's first value */
+    LSP_CONSTRAINT_TRANSITION = 3, /* when_transition: the check column's recurrence */
+    LSP_CONSTRAINT_LAST_ROW = 4   /* when_last_row: the check column's last value */
+};
+/* number of constraints LineaAIR::eval emits for this descriptor:
+ * 4 per permutation config, 4 + ntables per lookup config */
+int lsp_air_num_constraints(const int32_t *air, size_t air_len, uint32_t *n);
+/* constraint j -> its config's index and type (LSP_AIR_*), its kind
+ * (LSP_CONSTRAINT_*) and, for a lookup's b_inverse constraint, the table
+ * (-1 otherwise).  Any output may be NULL; LSP_E_ARG when j is past the end. */
+int lsp_air_constraint_info(const int32_t *air, size_t air_len, uint32_t j, uint32_t *config, int32_t *type,
+                            int32_t *kind, int32_t *table);
+/* failed_rows: rows with at least one violated constraint; violations: the
+ * (row, constraint) pairs violated; first_row / first_constraint: the lowest
+ * of them in (row, constraint) order -- what the reference's debug build
+ * panics on -- UINT64_MAX / UINT32_MAX when the trace satisfies the AIR */
+typedef struct { uint64_t failed_rows, violations, first_row; uint32_t first_constraint, ncons; } lsp_check_summary;
+/* value: the constraint's canonical value, Montgomery form like every element */
+typedef struct { uint64_t row; uint32_t constraint, reserved; lsp_fr value; } lsp_violation;
+/* The check over an h x w row-major trace (mem as in the prove call).  LSP_OK
+ * whenever the check ran; the verdict is in *summary (failed_rows == 0: the
+ * trace satisfies the AIR).  counts / first_rows: ncons entries each
+ * (lsp_air_num_constraints), nullable -- the rows violating constraint j and
+ * the lowest of them (UINT64_MAX: none).  list: the first `cap` violations in
+ * (row, constraint) order, nullable with cap = 0; *nlist (nullable when
+ * cap = 0) = how many were written.  LSP_E_ARG: a NULL argument, fewer than
+ * two public values, a bad descriptor, a column id >= w, or a height that is
+ * no power of two.  On a GPU context one kernel reads the trace once (thread
+ * i checks row i) and device memory beyond the trace is h/8 + O(ncons +
+ * cap * ncons) bytes of the context's pool; a host-only context
+ * (LSP_HOST_ONLY) checks host memory with a plain loop over the rows -- the
+ * same report, field for field -- and answers LSP_E_STATE for device memory.
+ * Setting LSP_CHECK_CONSTRAINTS=1 in the environment (read per call) makes
+ * the single-context prove call run this check first: on a violation it
+ * returns LSP_E_CONSTRAINT and the error message reads
+ *   constraints had nonzero value on row R: constraint J (config C, <kind>[, table T]); N rows fail
+ * Unset, proofs and their bytes are unchanged.  The group and sharded prove
+ * calls do not check: every rank holds the whole trace, so a caller checks
+ * it on any one context first. */
+int lsp_check_constraints(lsp_ctx *ctx, const lsp_fr *trace, size_t h, size_t w, const int32_t *air, size_t air_len,
+                          const lsp_fr *public_values, size_t npub, int mem, lsp_check_summary *summary,
+                          uint64_t *counts, uint64_t *first_rows, lsp_violation *list, size_t cap, size_t *nlist);
 
 /* ------------------------------------------------------------- PCS open */
 /* interpolate_coset [EXT p3-interpolation] of the first h rows of a bit-reversed

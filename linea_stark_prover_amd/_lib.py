@@ -12,9 +12,11 @@ import os
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LSP_LIB", os.path.join(_PKG, "_lib", "liblsp_hip.so"))
 
-LSP_OK, LSP_E_ARG, LSP_E_OOM, LSP_E_HIP, LSP_E_SIZE, LSP_E_VERIFY, LSP_E_STATE = range(7)
+LSP_OK, LSP_E_ARG, LSP_E_OOM, LSP_E_HIP, LSP_E_SIZE, LSP_E_VERIFY, LSP_E_STATE, LSP_E_CONSTRAINT = range(8)
 LSP_MEM_HOST, LSP_MEM_DEVICE = 0, 1
 LSP_AIR_PERMUTATION, LSP_AIR_LOOKUP = 1, 2
+(LSP_CONSTRAINT_B_INVERSE, LSP_CONSTRAINT_A_INVERSE, LSP_CONSTRAINT_FIRST_ROW, LSP_CONSTRAINT_TRANSITION,
+ LSP_CONSTRAINT_LAST_ROW) = range(5)
 
 c_fr_p = ctypes.c_void_p  # lsp_fr* (32-byte elements)
 
@@ -47,6 +49,18 @@ BCAST_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctyp
 class LspCommOps(ctypes.Structure):
     _fields_ = [("rank", ctypes.c_int), ("size", ctypes.c_int), ("user", ctypes.c_void_p),
                 ("allgather", ALLGATHER_FN), ("bcast", BCAST_FN)]
+
+
+class LspCheckSummary(ctypes.Structure):
+    """include/lsp.h lsp_check_summary"""
+    _fields_ = [("failed_rows", ctypes.c_uint64), ("violations", ctypes.c_uint64), ("first_row", ctypes.c_uint64),
+                ("first_constraint", ctypes.c_uint32), ("ncons", ctypes.c_uint32)]
+
+
+class LspViolation(ctypes.Structure):
+    """include/lsp.h lsp_violation"""
+    _fields_ = [("row", ctypes.c_uint64), ("constraint", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("value", ctypes.c_uint64 * 4)]
 
 
 class LspError(RuntimeError):
@@ -113,6 +127,15 @@ _SIGS = {
     "lsp_prove": (ctypes.c_int, [ctypes.c_void_p, c_fr_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p,
                                  ctypes.c_size_t, c_fr_p, ctypes.c_size_t, ctypes.c_int,
                                  ctypes.POINTER(ctypes.c_void_p)]),
+    "lsp_air_num_constraints": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)]),
+    "lsp_air_constraint_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,
+                                               ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32),
+                                               ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "lsp_check_constraints": (ctypes.c_int, [ctypes.c_void_p, c_fr_p, ctypes.c_size_t, ctypes.c_size_t,
+                                             ctypes.c_void_p, ctypes.c_size_t, c_fr_p, ctypes.c_size_t, ctypes.c_int,
+                                             ctypes.POINTER(LspCheckSummary), ctypes.POINTER(ctypes.c_uint64),
+                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(LspViolation),
+                                             ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "lsp_proof_serialize": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                            ctypes.POINTER(ctypes.c_size_t)]),
     "lsp_proof_free": (ctypes.c_int, [ctypes.c_void_p]),

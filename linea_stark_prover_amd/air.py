@@ -86,6 +86,21 @@ class LineaAIR:
             out += c.encode()
         return out
 
+    def constraint_names(self) -> List[str]:
+        """One name per constraint of ``LineaAIR::eval`` in its order (the
+        indexing of ``lsp_air_constraint_info`` and of a ``ConstraintReport``),
+        e.g. ``"cfg 2 lookup: b_inverse[1]"``, ``"cfg 5 permutation: transition"``."""
+        out = []
+        for k, c in enumerate(self.configs):
+            if isinstance(c, AirPermutationConfig):
+                kinds = ["b_inverse", "first_row", "transition", "last_row"]
+                out += [f"cfg {k} permutation: {x}" for x in kinds]
+            else:
+                kinds = (["a_inverse"] + [f"b_inverse[{t}]" for t in range(len(c.b_columns_ids))]
+                         + ["first_row", "transition", "last_row"])
+                out += [f"cfg {k} lookup: {x}" for x in kinds]
+        return out
+
     @staticmethod
     def from_descriptor(d: List[int]) -> "LineaAIR":
         it = iter(d)

@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <thread>
@@ -22,11 +23,13 @@ std::string bounds_fault_report() {
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return "";
     (void)hipDeviceSynchronize();  // the call's kernels are done (any stream)
     static const char* const files[] = {"k_ntt.hip", "k_hash.hip", "k_field.hip", "k_quotient.hip", "k_open.hip",
-                                        "k_witness.hip", "fr29.hpp", "k_common.hpp", "poseidon2_f29.hpp", "fr.hpp"};
+                                        "k_witness.hip", "k_check.hip", "fr29.hpp", "k_common.hpp", "poseidon2_f29.hpp",
+                                        "fr.hpp"};
     static unsigned (*const readers[])() = {bounds_fault_k_ntt, bounds_fault_k_hash, bounds_fault_k_field,
-                                            bounds_fault_k_quotient, bounds_fault_k_open, bounds_fault_k_witness};
+                                            bounds_fault_k_quotient, bounds_fault_k_open, bounds_fault_k_witness,
+                                            bounds_fault_k_check};
     static const char* const tus[] = {"k_ntt.hip", "k_hash.hip", "k_field.hip", "k_quotient.hip", "k_open.hip",
-                                      "k_witness.hip"};
+                                      "k_witness.hip", "k_check.hip"};
     std::string out;
     for (size_t t = 0; t < sizeof readers / sizeof readers[0]; ++t) {
         const unsigned v = readers[t]();
@@ -801,7 +804,68 @@ int lsp_prove(lsp_ctx* ctx, const lsp_fr* trace, size_t h, size_t w, const int32
         std::vector<Fr> pub(npub);
         for (size_t i = 0; i < npub; ++i) pub[i] = to_fr(pubv[i]);
         const Fr* din = dev_in(ctx, trace, h * w, mem, "trace_in");
+        // the reference's debug-build check_constraints, opt-in (read per call, as LSP_QUOTIENT_ORDER is)
+        if (const char* e = std::getenv("LSP_CHECK_CONSTRAINTS")) {
+            if (e[0] == '1' && !e[1]) {
+                const CheckReport r = check_constraints_device(ctx, din, h, w, A, pub.data(), npub, 0);
+                if (r.s.failed_rows) throw LspError(LSP_E_CONSTRAINT, check_failure_message(A, r));
+            }
+        }
         *out = prove_device(ctx, din, h, w, A, pub.data(), npub);
+    });
+}
+
+// ---------------------------------------------------- check_constraints
+int lsp_air_num_constraints(const int32_t* air, size_t air_len, uint32_t* n) {
+    return guarded(nullptr, [&] {
+        LSP_REQUIRE(n, LSP_E_ARG, "null");
+        *n = Air::parse(air, air_len).num_constraints();
+    });
+}
+
+int lsp_air_constraint_info(const int32_t* air, size_t air_len, uint32_t j, uint32_t* config, int32_t* type,
+                            int32_t* kind, int32_t* table) {
+    return guarded(nullptr, [&] {
+        const Air::ConsInfo ci = Air::parse(air, air_len).constraint_info(j);
+        if (config) *config = ci.config;
+        if (type) *type = ci.type;
+        if (kind) *kind = ci.kind;
+        if (table) *table = ci.table;
+    });
+}
+
+int lsp_check_constraints(lsp_ctx* ctx, const lsp_fr* trace, size_t h, size_t w, const int32_t* air, size_t air_len,
+                          const lsp_fr* pubv, size_t npub, int mem, lsp_check_summary* summary, uint64_t* counts,
+                          uint64_t* first_rows, lsp_violation* list, size_t cap, size_t* nlist) {
+    return guarded(ctx, [&] {
+        LSP_REQUIRE(ctx && trace && pubv && summary, LSP_E_ARG, "bad check_constraints arguments");
+        LSP_REQUIRE(cap == 0 || (list && nlist), LSP_E_ARG, "cap > 0 needs list and nlist");
+        LSP_REQUIRE(mem == LSP_MEM_HOST || mem == LSP_MEM_DEVICE, LSP_E_ARG,
+                    "mem must be LSP_MEM_HOST or LSP_MEM_DEVICE");
+        LSP_REQUIRE(npub >= 2, LSP_E_ARG, "public values must hold [alpha, delta]");
+        LSP_REQUIRE(h && !(h & (h - 1)), LSP_E_ARG, "trace height must be a power of two");
+        std::lock_guard<std::mutex> g(ctx->mu);
+        const Air A = Air::parse(air, air_len);
+        LSP_REQUIRE(A.max_col < w, LSP_E_ARG, "AIR column id outside the trace width");
+        std::vector<Fr> pub(npub);
+        for (size_t i = 0; i < npub; ++i) pub[i] = to_fr(pubv[i]);
+        CheckReport r;
+        if (ctx->device == LSP_HOST_ONLY && mem == LSP_MEM_HOST) {
+            // the host twin: a host-only context checks host memory (never a fallback on a GPU context)
+            static_assert(sizeof(Fr) == sizeof(lsp_fr), "lsp_fr is Fr's words");
+            std::vector<Fr> t(h * w);
+            std::memcpy(t.data(), trace, t.size() * sizeof(Fr));
+            r = check_constraints_host(t.data(), h, w, A, pub.data(), npub, cap);
+        } else {
+            need_gpu(ctx);
+            const Fr* din = dev_in(ctx, trace, h * w, mem, "trace_in");
+            r = check_constraints_device(ctx, din, h, w, A, pub.data(), npub, cap);
+        }
+        *summary = r.s;
+        if (counts) std::copy(r.counts.begin(), r.counts.end(), counts);
+        if (first_rows) std::copy(r.first_rows.begin(), r.first_rows.end(), first_rows);
+        if (nlist) *nlist = r.list.size();
+        if (cap) std::copy(r.list.begin(), r.list.end(), list);
     });
 }
 

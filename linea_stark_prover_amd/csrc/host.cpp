@@ -273,41 +273,37 @@ uint32_t Air::log_quotient_degree(int pd) const {
     return lg;
 }
 
-static Fr horner(const Fr* row, const int32_t* ids, size_t n, const Fr& a) {
-    Fr acc = fr_zero();
-    for (size_t i = 0; i < n; ++i) acc = fr_add(fr_mul(acc, a), row[ids[i]]);
-    return acc;
-}
-
 void Air::eval_fold(const Fr* loc, const Fr* nxt, const Fr& ap, const Fr& dl, const Fr& first, const Fr& last,
                     const Fr& trans, const Fr& al, Fr& acc) const {
-    const Fr one = fr_one();
-    auto push = [&](const Fr& x) { acc = fr_add(fr_mul(acc, al), x); };
-    for (const auto& g : cfgs) {
-        if (g.type == LSP_AIR_PERMUTATION) {
-            const Fr a_l = fr_add(horner(loc, g.a.data(), g.a.size(), ap), dl);
-            const Fr b_l = fr_add(horner(loc, g.b.data(), g.b.size(), ap), dl);
-            push(fr_sub(fr_mul(b_l, loc[g.binv]), one));
-            push(fr_mul(first, fr_sub(loc[g.check], fr_mul(a_l, loc[g.binv]))));
-            const Fr a_n = fr_add(horner(nxt, g.a.data(), g.a.size(), ap), dl);
-            push(fr_mul(trans, fr_sub(nxt[g.check], fr_mul(fr_mul(loc[g.check], a_n), nxt[g.binv]))));
-            push(fr_mul(last, fr_sub(loc[g.check], one)));
-        } else {
-            const Fr a_l = fr_add(horner(loc, g.a.data(), g.a.size(), ap), dl);
-            push(fr_sub(fr_mul(a_l, loc[g.a_inv]), one));
-            Fr lc = fr_mul(loc[g.a_filter], loc[g.a_inv]);
-            Fr nc = fr_mul(nxt[g.a_filter], nxt[g.a_inv]);
-            for (int32_t t = 0; t < g.ntab; ++t) {
-                const Fr b_l = fr_add(horner(loc, g.b.data() + t * g.nbc, g.nbc, ap), dl);
-                push(fr_sub(fr_mul(b_l, loc[g.b_inv[t]]), one));
-                lc = fr_sub(lc, fr_mul(fr_mul(loc[g.b_filter[t]], loc[g.occ[t]]), loc[g.b_inv[t]]));
-                nc = fr_sub(nc, fr_mul(fr_mul(nxt[g.b_filter[t]], nxt[g.occ[t]]), nxt[g.b_inv[t]]));
-            }
-            push(fr_mul(first, fr_sub(loc[g.check], lc)));
-            push(fr_mul(trans, fr_sub(fr_sub(nxt[g.check], loc[g.check]), nc)));
-            push(fr_mul(last, loc[g.check]));
+    eval(loc, nxt, ap, dl, first, last, trans, [&](const Fr& x) { acc = fr_add(fr_mul(acc, al), x); });
+}
+
+Air::ConsInfo Air::constraint_info(uint32_t j) const {
+    uint32_t k = 0;
+    for (size_t c = 0; c < cfgs.size(); ++c) {
+        const AirCfg& g = cfgs[c];
+        const uint32_t n = g.type == LSP_AIR_PERMUTATION ? 4 : 4 + (uint32_t)g.ntab;
+        if (j >= k + n) {
+            k += n;
+            continue;
         }
+        const uint32_t i = j - k;
+        ConsInfo o{(uint32_t)c, g.type, 0, -1};
+        if (g.type == LSP_AIR_PERMUTATION) {
+            static const int32_t kinds[4] = {LSP_CONSTRAINT_B_INVERSE, LSP_CONSTRAINT_FIRST_ROW,
+                                             LSP_CONSTRAINT_TRANSITION, LSP_CONSTRAINT_LAST_ROW};
+            o.kind = kinds[i];
+        } else if (i == 0) {
+            o.kind = LSP_CONSTRAINT_A_INVERSE;
+        } else if (i <= (uint32_t)g.ntab) {
+            o.kind = LSP_CONSTRAINT_B_INVERSE;
+            o.table = (int32_t)(i - 1);
+        } else {
+            o.kind = LSP_CONSTRAINT_FIRST_ROW + (int32_t)(i - 1 - (uint32_t)g.ntab);
+        }
+        return o;
     }
+    throw LspError(LSP_E_ARG, "constraint index past the AIR's last constraint");
 }
 
 }  // namespace lsp

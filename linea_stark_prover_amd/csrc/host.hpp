@@ -197,10 +197,59 @@ struct Air {
     // (max constraint degree, constraint count) under the U6 public-degree rule
     std::pair<int, int> stats(int public_degree) const;
     uint32_t log_quotient_degree(int public_degree) const;
+    // LineaAIR::eval on concrete values: push(x) gets every constraint's value
+    // (already multiplied by its selector) in eval's order
+    template <class Push>
+    void eval(const Fr* loc, const Fr* nxt, const Fr& ap, const Fr& dl, const Fr& first, const Fr& last,
+              const Fr& trans, Push&& push) const;
     // concrete evaluation folded into acc (verifier / tests)
     void eval_fold(const Fr* loc, const Fr* nxt, const Fr& ap, const Fr& dl, const Fr& first, const Fr& last,
                    const Fr& trans, const Fr& alpha, Fr& acc) const;
+    // what constraint j of eval's order is (lsp_air_constraint_info); LSP_E_ARG when j is past the end
+    struct ConsInfo {
+        uint32_t config;
+        int32_t type, kind, table;  // kind: LSP_CONSTRAINT_*; table: the lookup table of a b_inverse, else -1
+    };
+    uint32_t num_constraints() const { return (uint32_t)stats(0).second; }
+    ConsInfo constraint_info(uint32_t j) const;
 };
+
+inline Fr air_horner(const Fr* row, const int32_t* ids, size_t n, const Fr& a) {
+    Fr acc = fr_zero();
+    for (size_t i = 0; i < n; ++i) acc = fr_add(fr_mul(acc, a), row[ids[i]]);
+    return acc;
+}
+
+template <class Push>
+void Air::eval(const Fr* loc, const Fr* nxt, const Fr& ap, const Fr& dl, const Fr& first, const Fr& last,
+               const Fr& trans, Push&& push) const {
+    const Fr one = fr_one();
+    for (const auto& g : cfgs) {
+        if (g.type == LSP_AIR_PERMUTATION) {
+            const Fr a_l = fr_add(air_horner(loc, g.a.data(), g.a.size(), ap), dl);
+            const Fr b_l = fr_add(air_horner(loc, g.b.data(), g.b.size(), ap), dl);
+            push(fr_sub(fr_mul(b_l, loc[g.binv]), one));
+            push(fr_mul(first, fr_sub(loc[g.check], fr_mul(a_l, loc[g.binv]))));
+            const Fr a_n = fr_add(air_horner(nxt, g.a.data(), g.a.size(), ap), dl);
+            push(fr_mul(trans, fr_sub(nxt[g.check], fr_mul(fr_mul(loc[g.check], a_n), nxt[g.binv]))));
+            push(fr_mul(last, fr_sub(loc[g.check], one)));
+        } else {
+            const Fr a_l = fr_add(air_horner(loc, g.a.data(), g.a.size(), ap), dl);
+            push(fr_sub(fr_mul(a_l, loc[g.a_inv]), one));
+            Fr lc = fr_mul(loc[g.a_filter], loc[g.a_inv]);
+            Fr nc = fr_mul(nxt[g.a_filter], nxt[g.a_inv]);
+            for (int32_t t = 0; t < g.ntab; ++t) {
+                const Fr b_l = fr_add(air_horner(loc, g.b.data() + t * g.nbc, g.nbc, ap), dl);
+                push(fr_sub(fr_mul(b_l, loc[g.b_inv[t]]), one));
+                lc = fr_sub(lc, fr_mul(fr_mul(loc[g.b_filter[t]], loc[g.occ[t]]), loc[g.b_inv[t]]));
+                nc = fr_sub(nc, fr_mul(fr_mul(nxt[g.b_filter[t]], nxt[g.occ[t]]), nxt[g.b_inv[t]]));
+            }
+            push(fr_mul(first, fr_sub(loc[g.check], lc)));
+            push(fr_mul(trans, fr_sub(fr_sub(nxt[g.check], loc[g.check]), nc)));
+            push(fr_mul(last, loc[g.check]));
+        }
+    }
+}
 
 struct lsp_query {
     std::vector<Fr> trow, tpath, qrow, qpath, sib;

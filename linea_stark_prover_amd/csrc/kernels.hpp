@@ -223,6 +223,31 @@ hipError_t launch_quotient(const QuotientArgs& a, hipStream_t st);
 // wrote into a.cons (same points, thread order and bounds as launch_quotient)
 hipError_t launch_quotient_fold(const QuotientArgs& a, hipStream_t st);
 
+// -------------------------------------------------------- k_check.hip
+// p3-uni-stark check_constraints on the trace itself: thread i evaluates
+// LineaAIR::eval on local = row i, next = row (i + 1) mod h of the row-major
+// h x w trace with the 0/1 selectors first = (i == 0), last = (i == h - 1),
+// transition = (i != h - 1); constraints in eval's order (launch_quotient's)
+struct CheckArgs {
+    const Fr* trace;     // h x w row-major, natural order
+    uint64_t h;
+    uint32_t w;
+    const int32_t* air;  // device copy of the AIR descriptor
+    uint32_t ncons;
+    Fr pub_alpha, pub_delta;
+    // launch_check (the caller zeroes count and fills first_row with ~0):
+    uint64_t* row_mask;  // ceil(h / 64) words: bit i % 64 of word i / 64 = row i violates a constraint
+    uint64_t* count;     // ncons: rows violating constraint j
+    uint64_t* first_row; // ncons: the lowest of them
+    // launch_check_rows: thread t re-evaluates row rows[t], t < nrows, and
+    // writes constraint j's canonical value (0 under a 0 selector) to vals[t * ncons + j]
+    const uint64_t* rows = nullptr;
+    uint32_t nrows = 0;
+    Fr* vals = nullptr;
+};
+hipError_t launch_check(const CheckArgs& a, hipStream_t st);
+hipError_t launch_check_rows(const CheckArgs& a, hipStream_t st);
+
 // --------------------------------------------------------- k_open.hip
 // den[i] = z - GEN * w_N^bitrev(row0 + i) for i < n (two-level table of w_N)
 hipError_t launch_open_denoms(Fr z, Fr gen, const Fr* tabN, uint32_t L1, uint32_t logN, size_t n, Fr* den,
@@ -272,6 +297,7 @@ unsigned bounds_fault_k_field();
 unsigned bounds_fault_k_quotient();
 unsigned bounds_fault_k_open();
 unsigned bounds_fault_k_witness();
+unsigned bounds_fault_k_check();
 #endif
 // one matrix opened at npts points (the generic reduce of TwoAdicFriPcs::open):
 // ro[i] += sum_p (offys[p] - off[p] * sum_c apw[c] M[i][c]) * inv[p*n + i]

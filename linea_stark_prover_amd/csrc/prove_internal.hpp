@@ -27,6 +27,20 @@ Fr commit_device(lsp_ctx* ctx, const MatList& m, size_t height, Fr* layers, cons
                  const std::function<void(hipEvent_t)>* side = nullptr);
 lsp_proof* prove_device(lsp_ctx* ctx, const Fr* d_trace, size_t h, size_t w, const Air& air, const Fr* pub,
                         size_t npub);
+// p3-uni-stark check_constraints over the h x w trace (check.cpp): the device
+// path (k_check.hip; d_trace on ctx's GPU) and the host loop fill the same
+// report; list = the first `cap` violations in (row, constraint) order
+struct CheckReport {
+    lsp_check_summary s;
+    std::vector<uint64_t> counts, first_rows;  // per constraint; first_rows UINT64_MAX = none
+    std::vector<lsp_violation> list;
+};
+CheckReport check_constraints_device(lsp_ctx* ctx, const Fr* d_trace, size_t h, size_t w, const Air& air,
+                                     const Fr* pub, size_t npub, size_t cap);
+CheckReport check_constraints_host(const Fr* trace, size_t h, size_t w, const Air& air, const Fr* pub, size_t npub,
+                                   size_t cap);
+// "constraints had nonzero value on row R: constraint J (config C, <kind>[, table T]); N rows fail"
+std::string check_failure_message(const Air& air, const CheckReport& r);
 struct Comm;
 // one rank of a proof sharded over comm.size ranks (prove_device = 1 rank);
 // every rank returns the same proof

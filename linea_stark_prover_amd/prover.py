@@ -71,6 +71,55 @@ class StarkConfig:
         return a, d, rc
 
 
+_NONE64 = (1 << 64) - 1
+
+
+@dataclass
+class Violation:
+    row: int
+    index: int   # the constraint, numbered as LineaAIR.constraint_names()
+    name: str
+    value: int   # the constraint's canonical value on that row (nonzero)
+
+
+@dataclass
+class ConstraintReport:
+    """What p3-uni-stark's check_constraints found on a trace
+    (lsp_check_constraints): rows are trace rows, constraints are numbered in
+    LineaAIR::eval's order (LineaAIR.constraint_names())."""
+    ok: bool
+    failed_rows: int                  # rows with at least one violated constraint
+    violations: int                   # violated (row, constraint) pairs
+    first: Optional[Tuple[int, int]]  # the lowest (row, constraint): the reference's debug-build panic
+    counts: List[int]                 # per constraint: rows violating it
+    first_rows: List[Optional[int]]   # per constraint: the lowest of them
+    details: List[Violation]          # the first max_violations of them in (row, constraint) order
+    names: List[str]
+
+    def __str__(self) -> str:
+        if self.ok:
+            return f"constraints hold ({len(self.counts)} constraints)"
+        r, j = self.first
+        lines = [f"constraints had nonzero value on row {r}: constraint {j} ({self.names[j]}); "
+                 f"{self.failed_rows} rows fail, {self.violations} violations"]
+        for j, (n, fr) in enumerate(zip(self.counts, self.first_rows)):
+            if n:
+                lines.append(f"  constraint {j:3d} {self.names[j]}: {n} rows, first row {fr}")
+        for v in self.details:
+            lines.append(f"  row {v.row} constraint {v.index} ({v.name}) = {v.value:#x}")
+        if len(self.details) < self.violations:
+            lines.append(f"  ... {self.violations - len(self.details)} more")
+        return "\n".join(lines)
+
+
+class ConstraintError(ValueError):
+    """prove(check=True) on a trace that violates the AIR; .report is the ConstraintReport"""
+
+    def __init__(self, report: ConstraintReport):
+        super().__init__(str(report))
+        self.report = report
+
+
 def _take_proof(proof: ctypes.c_void_p, size_only: bool = False):
     """serialize and free an lsp_proof handle (size_only: its wire size, the
     one thing a rehearsal proof answers).  The library writes into a bytearray
@@ -278,11 +327,55 @@ class Context:
         self._chk(L.lib().lsp_batch_inverse(self.h, _ptr(x), x.shape[0], _ptr(out), L.LSP_MEM_HOST))
         return out
 
+    # ----------------------------------------------------- check_constraints
+    def check_constraints(self, trace, air: LineaAIR, public_values: np.ndarray, h: Optional[int] = None,
+                          w: Optional[int] = None, max_violations: int = 16) -> ConstraintReport:
+        """p3-uni-stark's check_constraints (the reference's debug-build check
+        inside prove): which rows of the trace break which constraints.
+        `trace` as in prove: an (h, w, 4) host array, or a device pointer (int)
+        with h and w given.  A host-only context (device=-1) checks a host
+        array on the CPU."""
+        desc = (ctypes.c_int32 * len(air.descriptor()))(*air.descriptor())
+        pub = _fr_arr(public_values).reshape(-1, 4)
+        nc = ctypes.c_uint32()
+        L.check(L.lib().lsp_air_num_constraints(desc, len(desc), ctypes.byref(nc)))
+        s, nl = L.LspCheckSummary(), ctypes.c_size_t()
+        counts, firsts = (ctypes.c_uint64 * max(nc.value, 1))(), (ctypes.c_uint64 * max(nc.value, 1))()
+        cap = max(int(max_violations), 0)
+        lst = (L.LspViolation * max(cap, 1))()
+        if isinstance(trace, int):
+            tp, mem = trace, L.LSP_MEM_DEVICE
+        else:
+            t = _fr_arr(trace)
+            tp, h, w, mem = _ptr(t), t.shape[0], t.shape[1], L.LSP_MEM_HOST
+        self._chk(L.lib().lsp_check_constraints(self.h, tp, h, w, desc, len(desc), _ptr(pub), pub.shape[0], mem,
+                                                ctypes.byref(s), counts, firsts, lst, cap, ctypes.byref(nl)))
+        names = air.constraint_names()
+        assert len(names) == s.ncons == nc.value
+        from .field import from_mont
+        vals = from_mont(np.array([list(lst[i].value) for i in range(nl.value)], np.uint64).reshape(-1, 4))
+        details = [Violation(int(lst[i].row), int(lst[i].constraint), names[lst[i].constraint], vals[i])
+                   for i in range(nl.value)]
+        ok = s.failed_rows == 0
+        return ConstraintReport(ok=ok, failed_rows=int(s.failed_rows), violations=int(s.violations),
+                                first=None if ok else (int(s.first_row), int(s.first_constraint)),
+                                counts=[int(counts[j]) for j in range(nc.value)],
+                                first_rows=[None if firsts[j] == _NONE64 else int(firsts[j])
+                                            for j in range(nc.value)],
+                                details=details, names=names)
+
     # ----------------------------------------------------------------- prove
     def prove(self, trace, air: LineaAIR, public_values: np.ndarray, h: Optional[int] = None,
-              w: Optional[int] = None) -> bytes:
+              w: Optional[int] = None, check: bool = False) -> bytes:
         """p3_uni_stark::prove.  `trace` is an (h, w, 4) host array, or a device
-        pointer (int) to an h x w matrix with h and w given."""
+        pointer (int) to an h x w matrix with h and w given.  check=True runs
+        check_constraints first and raises ConstraintError(report) instead of
+        proving a trace that violates the AIR (a development switch, as the
+        reference's debug-build check is)."""
+        if check:
+            report = self.check_constraints(trace, air, public_values, h, w)
+            if not report.ok:
+                raise ConstraintError(report)
         desc = (ctypes.c_int32 * len(air.descriptor()))(*air.descriptor())
         pub = _fr_arr(public_values).reshape(-1, 4)
         proof = ctypes.c_void_p()
@@ -581,12 +674,13 @@ class ProverGroup:
 
 
 def prove(config: StarkConfig, air: LineaAIR, trace: np.ndarray, public_values: np.ndarray,
-          ctx: Optional[Context] = None) -> bytes:
-    """p3_uni_stark::prove(&config, &air, &mut challenger, trace, &public_values)."""
+          ctx: Optional[Context] = None, check: bool = False) -> bytes:
+    """p3_uni_stark::prove(&config, &air, &mut challenger, trace, &public_values);
+    check=True: check_constraints first (Context.prove)."""
     own = ctx is None
     ctx = ctx or Context(config)
     try:
-        return ctx.prove(trace, air, public_values)
+        return ctx.prove(trace, air, public_values, check=check)
     finally:
         if own:
             ctx.close()
@@ -604,4 +698,5 @@ def verify(config: StarkConfig, air: LineaAIR, proof: bytes, public_values: np.n
 
 
 __all__ = ["StarkConfig", "Context", "Radix2DitParallel", "MerkleTreeMmcs", "MerkleTree",
-           "TwoAdicFriGenericConfig", "gen_permutation_trace", "gen_wide_trace", "prove", "verify", "to_mont"]
+           "TwoAdicFriGenericConfig", "gen_permutation_trace", "gen_wide_trace", "prove", "verify", "to_mont",
+           "ConstraintReport", "ConstraintError", "Violation"]

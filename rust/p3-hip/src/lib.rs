@@ -26,7 +26,7 @@ mod proof;
 pub use dft::HipDft;
 pub use fri::HipFriFolder;
 pub use mmcs::{HipMmcs, HipMmcsError, HipTree};
-pub use proof::{from_proof, prove, proof_from_bytes, proof_to_bytes, to_proof, try_from_proof};
+pub use proof::{check_constraints, from_proof, prove, proof_from_bytes, proof_to_bytes, to_proof, try_from_proof};
 
 use std::ffi::CStr;
 use std::ptr::NonNull;

@@ -298,6 +298,10 @@ where
 /// (`bin/src/main.rs:80-86`) on the GPU.  `air` is the AIR descriptor
 /// (INTEGRATION.md `air_descriptor`), `public_values` = `[alpha, delta]`.
 /// The result goes to `p3_uni_stark::verify` unchanged (`bin/src/main.rs:88-96`).
+///
+/// A debug build first runs p3-uni-stark's `check_constraints` on the GPU
+/// (`lsp_check_constraints`), as `p3_uni_stark::prove` does under
+/// `#[cfg(debug_assertions)]`, and panics with the first failing row.
 pub fn prove<SC>(
     ctx: &Ctx,
     trace: &p3_matrix::dense::RowMajorMatrix<Val>,
@@ -309,6 +313,8 @@ where
     Proof<SC>: DeserializeOwned,
 {
     use p3_matrix::Matrix;
+    #[cfg(debug_assertions)]
+    check_constraints(ctx, trace, air, public_values);
     let mut out: *mut sys::lsp_proof = std::ptr::null_mut();
     let rc = unsafe {
         sys::lsp_prove(
@@ -328,4 +334,61 @@ where
     let p = to_proof::<SC>(out);
     unsafe { sys::lsp_proof_free(out) };
     p
+}
+
+/// p3-uni-stark's `check_constraints(air, &trace, public_values)` on the GPU:
+/// panics with the first (row, constraint) the trace violates, in the
+/// library's wording of the reference's debug-build panic.
+pub fn check_constraints(ctx: &Ctx, trace: &p3_matrix::dense::RowMajorMatrix<Val>, air: &[i32], public_values: &[Val]) {
+    use p3_matrix::Matrix;
+    let mut s = sys::lsp_check_summary::default();
+    let rc = unsafe {
+        sys::lsp_check_constraints(
+            ctx.raw(),
+            fr_ptr(&trace.values),
+            trace.height(),
+            trace.width(),
+            air.as_ptr(),
+            air.len(),
+            fr_ptr(public_values),
+            public_values.len(),
+            sys::LSP_MEM_HOST,
+            &mut s,
+            std::ptr::null_mut(),
+            std::ptr::null_mut(),
+            std::ptr::null_mut(),
+            0,
+            std::ptr::null_mut(),
+        )
+    };
+    ctx.check(rc, "lsp_check_constraints");
+    if s.failed_rows != 0 {
+        let (mut config, mut kind, mut table) = (0u32, 0i32, -1i32);
+        check_global(
+            unsafe {
+                sys::lsp_air_constraint_info(
+                    air.as_ptr(),
+                    air.len(),
+                    s.first_constraint,
+                    &mut config,
+                    std::ptr::null_mut(),
+                    &mut kind,
+                    &mut table,
+                )
+            },
+            "lsp_air_constraint_info",
+        );
+        let kind = match kind {
+            sys::LSP_CONSTRAINT_B_INVERSE => "b_inverse",
+            sys::LSP_CONSTRAINT_A_INVERSE => "a_inverse",
+            sys::LSP_CONSTRAINT_FIRST_ROW => "first_row",
+            sys::LSP_CONSTRAINT_TRANSITION => "transition",
+            _ => "last_row",
+        };
+        let table = if table >= 0 { format!(", table {table}") } else { String::new() };
+        panic!(
+            "constraints had nonzero value on row {}: constraint {} (config {config}, {kind}{table}); {} rows fail",
+            s.first_row, s.first_constraint, s.failed_rows
+        );
+    }
 }
