@@ -44,7 +44,7 @@ struct Comm {
     int rank = 0, size = 1;
     double init_ms = 0;          // communicator creation (RCCL: ncclCommInitRank), wall ms
     std::vector<CommRec> log;    // the collectives since the last begin_log()
-    // Exchange calibration (lsp_comm_selftest, calibrate_exchange in prove.cpp),
+    // Exchange calibration (lsp_comm_selftest, calibrate_exchange in exchange.cpp),
     // the minimum over the ranks so every rank plans the same collectives:
     // allgather bandwidth into one rank ((G - 1) shares / wall time, GB/s), the
     // inverse NTT's rate on this GPU (G elements/s), and the probe's size.

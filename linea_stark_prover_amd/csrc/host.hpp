@@ -300,7 +300,11 @@ struct Comm;
 // so a dispatch must cost microseconds, not a condition-variable wake-up per
 // level -- workers spin on the job generation for a short window after each
 // job (kSpinUs) before sleeping, and the caller spins for completion.
-class HostPool {
+// On cache lines of its own: the spinning workers poll gen_, and a neighbour
+// on the heap sharing that line made every store to the neighbour (the
+// transcript's buffers while the query indices are sampled: 105 -> 150-220 us
+// at 2^19) fight 15 readers for it.
+class alignas(64) HostPool {
   public:
     explicit HostPool(unsigned workers);
     ~HostPool();
@@ -354,7 +358,7 @@ struct lsp_ctx {
     std::map<std::string, Buf> pool;
     std::map<std::string, Buf> hpool;  // pinned host staging buffers (hbuf)
     std::map<std::string, hipEvent_t> stage_ev;  // last copy out of each h2d_async staging buffer
-    hipEvent_t ev_near = nullptr, ev_top = nullptr;  // tree-top hand-off (prove.cpp commit_device)
+    hipEvent_t ev_near = nullptr, ev_top = nullptr;  // tree-top hand-off (merkle.cpp commit_device)
     hipEvent_t ev_warm = nullptr;  // after a tree's wide levels: the host pool starts spinning (commit_device)
     // work beside a tree's narrow levels (prove.cpp, "constraints before alpha"):
     // a low-priority stream, the event after the tree's wide levels it waits
@@ -369,10 +373,10 @@ struct lsp_ctx {
     bool phase_timing = true;
     std::vector<std::string> phase_only;
     std::map<std::pair<uint32_t, int>, uint4*> twiddles;
-    std::map<std::string, const lsp::Fr*> ptabs;  // cached power tables (prove.cpp pow_table), pool-owned
+    std::map<std::string, const lsp::Fr*> ptabs;  // cached power tables (lde.cpp pow_table), pool-owned
     // Inside lsp_prove the host-made tree-top layers are only read by the query
     // gather at the end, so their uploads wait there instead of delaying the next
-    // kernel on the stream (prove.cpp commit_device / flush_top_uploads).
+    // kernel on the stream (merkle.cpp commit_device / flush_top_uploads).
     struct TopUpload {
         void* dst;
         const void* src;

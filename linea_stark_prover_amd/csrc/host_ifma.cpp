@@ -1,6 +1,6 @@
 // Poseidon2Bls12337<3> on the host, 8 permutations at a time with AVX-512 IFMA
 // (vpmadd52luq / vpmadd52huq): the Merkle tree tops the host finishes
-// (prove.cpp commit_device) are many independent compressions per level, so
+// (merkle.cpp commit_device) are many independent compressions per level, so
 // eight lanes of 52-bit multiply-adds cover eight of them for about the cost
 // of one scalar 4 x 64-bit permutation (poseidon2_host64.hpp).
 //

@@ -1,10 +1,52 @@
 #pragma once
+#include <chrono>
 #include <functional>
+#include <string>
 #include <vector>
 
 #include "host.hpp"
 
 namespace lsp {
+struct Comm;
+// LSP_TIME_TOPS=1 (merkle.cpp): host-side timing of the tree tops, the FRI
+// host tail and the query phase, printed to stderr
+bool time_tops();
+using host_clock = std::chrono::steady_clock;
+inline double us(host_clock::time_point a, host_clock::time_point b) {
+    return std::chrono::duration<double, std::micro>(b - a).count();
+}
+// ---- lde.cpp
+// two-level power table of `base` covering exponents < 2^bits, cached in the context
+const Fr* pow_table(lsp_ctx* ctx, const std::string& name, const Fr& base, uint32_t bits, uint32_t& L1);
+Fr d2h_fr(lsp_ctx* ctx, const Fr* d);  // one element from the device (synchronises the stream)
+// coset blocks [k0, k0 + nk) of the LDE from h * coefficients (natural order) at `coef`, laid out as `map` says
+void lde_coeffs_device(lsp_ctx* ctx, const Fr* coef, ColMap map, size_t h, size_t w, uint32_t added_bits,
+                       const Fr* shifts_host, Fr* d_out, uint32_t k0, uint32_t nk, bool div_h = true);
+// block `blk` (N / 2^b < h rows) of the N-row LDE, folded from the coefficients; buffers named after `tag`
+void subcoset_lde(lsp_ctx* ctx, const Fr* coef, ColMap map, size_t h, size_t w, uint32_t logN, uint32_t b,
+                  uint32_t blk, const Fr* shifts_host, Fr* d_out, const std::string& tag);
+// ---- merkle.cpp
+// one per proof in flight, for the proof's whole duration (the tree tops share the host's cores)
+struct ActiveProof {
+    ActiveProof();
+    ~ActiveProof();
+};
+// defers the tree-top uploads of one proof until flush_top_uploads; the
+// destructor drops any left (an error path)
+struct DeferTopUploads {
+    lsp_ctx* ctx;
+    explicit DeferTopUploads(lsp_ctx* c);
+    ~DeferTopUploads();
+};
+void flush_top_uploads(lsp_ctx* ctx);
+// the levels above `first` digests host[0, first) on the host pool; returns the
+// end of the layers.  pairs (optional): the digests are made first, as
+// compress(pairs[2i], pairs[2i+1])
+size_t host_levels(lsp_ctx* ctx, Fr* host, size_t first, host_clock::time_point* t_first = nullptr,
+                   const Fr* pairs = nullptr);
+// root of a tree whose bottom subtrees live on comm's ranks (`local` = this
+// rank's); `top` gets the host layers above the subtrees
+Fr shard_root(lsp_ctx* ctx, Comm& comm, const Fr& local, std::vector<std::vector<Fr>>& top, const char* tag);
 // coset LDE of an h x w device matrix with per-column shifts -> (h << added_bits) x w bit-reversed rows;
 // with nk > 0 only the coset blocks [k0, k0 + nk) (rows k0*h .. (k0+nk)*h - 1 of the full result)
 void lde_device(lsp_ctx* ctx, const Fr* d_in, size_t h, size_t w, uint32_t added_bits, const Fr* shifts_host,
@@ -13,11 +55,11 @@ void lde_device(lsp_ctx* ctx, const Fr* d_in, size_t h, size_t w, uint32_t added
 // coefficients -> evaluations on shift H_h stored bit-reversed, and natural-order evaluations -> coefficients
 void coset_dft_device(lsp_ctx* ctx, const Fr* d_coef, size_t h, size_t w, const Fr& shift, Fr* d_out);
 void coset_idft_device(lsp_ctx* ctx, const Fr* d_evals, size_t h, size_t w, const Fr& shift, Fr* d_out);
+// the pending phase events of the last proof -> ctx->timings (prove.cpp)
+void resolve_timings(lsp_ctx* ctx);
 // leaves + every layer into `layers` (2*height - 1); returns the root
 // fold: when set, the leaves are the pairs of the FRI fold it describes (fused
 // into the leaf kernel; m.ptr[0] receives the folded vector)
-// the pending phase events of the last proof -> ctx->timings (prove.cpp)
-void resolve_timings(lsp_ctx* ctx);
 // side (optional): called once, after the tree's launches are issued and before
 // the host waits for them, with an event on the context's stream that follows
 // the leaves and the wide levels (every level of more than 2^15 digests): work
@@ -41,7 +83,6 @@ CheckReport check_constraints_host(const Fr* trace, size_t h, size_t w, const Ai
                                    size_t cap);
 // "constraints had nonzero value on row R: constraint J (config C, <kind>[, table T]); N rows fail"
 std::string check_failure_message(const Air& air, const CheckReport& r);
-struct Comm;
 // one rank of a proof sharded over comm.size ranks (prove_device = 1 rank);
 // every rank returns the same proof
 lsp_proof* prove_shard(lsp_ctx* ctx, Comm& comm, const Fr* d_trace, size_t h, size_t w, const Air& air,

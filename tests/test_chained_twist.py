@@ -1,5 +1,5 @@
 """The chained coset twist of the fused LDE pass (k_ntt.hip k_ntt_rm,
-prove.cpp chain_ratio), CPU only:
+lde.cpp chain_ratio), CPU only:
 
   * the block order: blocks k0 + bitrev_a(j), j < nk = 2^a (k0 a multiple of
     nk), of the bit-reversed LDE of 2^b blocks have the coset shifts

@@ -136,7 +136,7 @@ def test_hash_rows_matches_sponge(gpu_ctx, oracle_lib, w):
 
 
 # ---------------------------------------------------------------- Merkle
-# heights cover every host tree-top path (prove.cpp host_levels): below one
+# heights cover every host tree-top path (merkle.cpp host_levels): below one
 # 16-digest subtree (2^3), one subtree (2^4), 16 subtree tasks (2^8), wide levels
 # first (2^9 .. 2^13), and trees hashed wholly on the host (h <= 1024, one matrix)
 @pytest.mark.parametrize("logh,widths", [(0, [3]), (1, [2]), (3, [2]), (4, [8]), (5, [1]), (8, [2]), (9, [3]),
