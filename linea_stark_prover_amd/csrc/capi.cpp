@@ -101,6 +101,13 @@ void finish_out(lsp_ctx* ctx, lsp_fr* p, const Fr* d, size_t n, int mem) {
     ctx->sync();
 }
 
+// n caller elements (public values, opened values) as Fr
+std::vector<Fr> to_frs(const lsp_fr* p, size_t n) {
+    std::vector<Fr> v(n);
+    for (size_t i = 0; i < n; ++i) v[i] = to_fr(p[i]);
+    return v;
+}
+
 void need_gpu(lsp_ctx* ctx) {
     LSP_REQUIRE(ctx, LSP_E_ARG, "null ctx");
     LSP_REQUIRE(ctx->device != LSP_HOST_ONLY, LSP_E_STATE, "host-only context (LSP_HOST_ONLY) has no GPU");
@@ -451,11 +458,7 @@ int lsp_hash_rows(lsp_ctx* ctx, const lsp_fr* rows, size_t n, size_t w, lsp_fr* 
         need_gpu(ctx);
         const Fr* din = dev_in(ctx, rows, n * w, mem, "api_in");
         Fr* dout = dev_out(ctx, out, n, mem, "api_out");
-        MatList m{};
-        m.ptr[0] = din;
-        m.width[0] = (uint32_t)w;
-        m.n = 1;
-        LSP_HIP(launch_hash_rows(m, n, dout, ctx->rc29_dev, ctx->p2.L, ctx->stream));
+        LSP_HIP(launch_hash_rows(one_mat(din, (uint32_t)w), n, dout, ctx->rc29_dev, ctx->p2.L, ctx->stream));
         finish_out(ctx, out, dout, n, mem);
     });
 }
@@ -577,14 +580,10 @@ int lsp_fri_fold(lsp_ctx* ctx, const lsp_fr* v, size_t len, const lsp_fr* beta, 
         const size_t m = len / 2;
         const Fr* din = dev_in(ctx, v, len, mem, "api_in");
         Fr* dout = dev_out(ctx, out, m, mem, "api_out");
-        const Fr half = fr_inv(fr_from_u64(2));
-        const Fr ginv = fr_inv(host_two_adic_generator(lg));
-        uint32_t L1 = (lg - 1 + 1) / 2, L2 = (lg - 1) - L1;
-        Fr* tab = ctx->fbuf("api_tab", (1ull << L1) + (1ull << L2));
-        Fr* b = ctx->fbuf("api_tab_base", 1);
-        LSP_HIP(hipMemcpyAsync(b, &ginv, sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-        LSP_HIP(launch_pow_tables(b, 1, L1, L2, nullptr, tab, ctx->stream));
-        LSP_HIP(launch_fri_fold(din, m, half, fr_mul(to_fr(*beta), half), tab, L1, dout, ctx->stream));
+        FoldSpec f = fold_spec(ctx, lg - 1, 0, to_fr(*beta));
+        f.v = din;
+        f.vout = dout;
+        fri_fold(ctx, f, m);
         finish_out(ctx, out, dout, m, mem);
     });
 }
@@ -616,53 +615,16 @@ int lsp_quotient_values(lsp_ctx* ctx, const lsp_fr* lde, size_t h, size_t w, con
         const uint32_t log_h = log2_exact(h), log_q = A.log_quotient_degree(ctx->public_degree);
         const uint32_t logQ = log_h + log_q;
         LSP_REQUIRE(log_q <= ctx->log_blowup, LSP_E_ARG, "quotient degree exceeds blowup");
-        const size_t N = h << ctx->log_blowup, Q = (size_t)1 << logQ, q = (size_t)1 << log_q;
+        const size_t N = h << ctx->log_blowup, Q = (size_t)1 << logQ;
         const Fr* dlde = dev_in(ctx, lde, N * w, mem, "api_in");
         Fr* dout = dev_out(ctx, out, Q, mem, "api_out");
-        const Fr GEN = host_generator(), one = fr_one();
-        const Fr wh_inv = fr_inv(host_two_adic_generator(log_h));
-        uint32_t L1 = (logQ + 1) / 2, L2 = logQ - L1;
-        Fr* tab = ctx->fbuf("api_tab", (1ull << L1) + (1ull << L2));
-        Fr* b = ctx->fbuf("api_tab_base", 1);
-        const Fr gq = host_two_adic_generator(logQ);
-        LSP_HIP(hipMemcpyAsync(b, &gq, sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-        LSP_HIP(launch_pow_tables(b, 1, L1, L2, nullptr, tab, ctx->stream));
-        Fr* den = ctx->fbuf("q_den", Q);
-        Fr* inv_den = ctx->fbuf("q_invden", Q);
-        LSP_HIP(launch_selector_denoms(tab, L1, GEN, wh_inv, Q, den, ctx->stream));
-        LSP_HIP(launch_batch_inverse(den, inv_den, Q, ctx->stream, ctx->bi_scratch(Q)));
-        std::vector<Fr> zz(2 * q);
-        const Fr gh = fr_pow_u64(GEN, h), gl = host_two_adic_generator(log_q);
-        Fr gg = one;
-        for (size_t k = 0; k < q; ++k) {
-            zz[k] = fr_sub(fr_mul(gh, gg), one);
-            zz[q + k] = fr_inv(zz[k]);
-            gg = fr_mul(gg, gl);
-        }
-        Fr* dz = ctx->fbuf("q_zh", 2 * q);
-        LSP_HIP(hipMemcpyAsync(dz, zz.data(), zz.size() * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-        int32_t* dair = (int32_t*)ctx->buf("air", A.raw.size() * sizeof(int32_t));
-        LSP_HIP(hipMemcpyAsync(dair, A.raw.data(), A.raw.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                               ctx->stream));
         QuotientArgs qa;
+        quotient_domain(ctx, log_h, log_q, 0, 0, Q, A, to_fr(pubv[0]), to_fr(pubv[1]), qa);
         qa.lde = dlde;
         qa.w = (uint32_t)w;
-        qa.logQ = logQ;
-        qa.log_q = log_q;
-        qa.air = dair;
-        qa.air_len = (uint32_t)A.raw.size();
-        qa.pub_alpha = to_fr(pubv[0]);
-        qa.pub_delta = to_fr(pubv[1]);
         qa.alpha = to_fr(*alpha);
-        qa.gen = GEN;
-        qa.wh_inv = wh_inv;
-        qa.tabQ = tab;
-        qa.L1 = L1;
-        qa.zh = dz;
-        qa.inv_zh = dz + q;
-        qa.inv_den = inv_den;
         qa.out = dout;
-        qa.lde_rows = (uint64_t)h << ctx->log_blowup;
+        qa.lde_rows = N;
         LSP_HIP(launch_quotient(qa, ctx->stream));
         finish_out(ctx, out, dout, Q, mem);
     });
@@ -677,26 +639,14 @@ int lsp_interpolate_coset(lsp_ctx* ctx, const lsp_fr* lde_bitrev, size_t h, size
         const uint32_t logh = log2_exact(h);
         const Fr* dm = dev_in(ctx, lde_bitrev, h * w, mem, "api_in");
         const Fr S = to_fr(*shift), Z = to_fr(*z);
-        uint32_t L1 = (logh + 1) / 2, L2 = logh - L1;
-        Fr* tab = ctx->fbuf("api_tab", (1ull << L1) + (1ull << L2));
-        Fr* b = ctx->fbuf("api_tab_base", 1);
-        const Fr gh = host_two_adic_generator(logh);
-        LSP_HIP(hipMemcpyAsync(b, &gh, sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-        LSP_HIP(launch_pow_tables(b, 1, L1, L2, nullptr, tab, ctx->stream));
-        Fr* den = ctx->fbuf("o_den", h);
         Fr* inv = ctx->fbuf("o_invz", h);
-        LSP_HIP(launch_open_denoms(Z, S, tab, L1, logh, h, den, ctx->stream));
-        LSP_HIP(launch_batch_inverse(den, inv, h, ctx->stream, ctx->bi_scratch(h)));
-        Fr* partial = ctx->fbuf("o_partial", ((h + 1023) / 1024) * w);
         Fr* sums = ctx->fbuf("o_sums", w);
-        uint32_t nb = 0;
-        LSP_HIP(launch_interp_partial(dm, (uint32_t)w, h, inv, S, tab, L1, logh, partial, &nb, ctx->stream));
-        LSP_HIP(launch_sum_partials(partial, nb, (uint32_t)w, sums, ctx->stream));
+        open_denominators(ctx, Z, S, logh, 0, h, inv);
+        barycentric_sums(ctx, dm, (uint32_t)w, h, inv, S, logh, 0, sums);
         std::vector<Fr> hs(w);
         LSP_HIP(hipMemcpyAsync(hs.data(), sums, w * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
         ctx->sync();
-        const Fr sh = fr_pow_u64(S, h);
-        const Fr f = fr_mul(fr_sub(fr_pow_u64(Z, h), sh), fr_inv(fr_mul(sh, fr_from_u64(h))));
+        const Fr f = CosetFactor(S, h, false).at(Z);
         for (size_t c = 0; c < w; ++c) ys_out[c] = from_fr(fr_mul(hs[c], f));
     });
 }
@@ -743,17 +693,8 @@ int lsp_inverse_denominators(lsp_ctx* ctx, const lsp_fr* points, size_t npoints,
         need_gpu(ctx);
         const size_t N = (size_t)1 << log_n;
         Fr* dout = dev_out(ctx, out, npoints * N, mem, "api_out");
-        uint32_t L1 = (log_n + 1) / 2, L2 = log_n - L1;
-        Fr* tab = ctx->fbuf("api_tab", (1ull << L1) + (1ull << L2));
-        Fr* b = ctx->fbuf("api_tab_base", 1);
-        const Fr gN = host_two_adic_generator(log_n);
-        LSP_HIP(hipMemcpyAsync(b, &gN, sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-        LSP_HIP(launch_pow_tables(b, 1, L1, L2, nullptr, tab, ctx->stream));
-        Fr* den = ctx->fbuf("o_den", npoints * N);
         for (size_t p = 0; p < npoints; ++p)
-            LSP_HIP(launch_open_denoms(to_fr(points[p]), to_fr(*shift), tab, L1, log_n, N, den + p * N,
-                                       ctx->stream));
-        LSP_HIP(launch_batch_inverse(den, dout, npoints * N, ctx->stream, ctx->bi_scratch(npoints * N)));
+            open_denominators(ctx, to_fr(points[p]), to_fr(*shift), log_n, 0, N, dout + p * N);
         finish_out(ctx, out, dout, npoints * N, mem);
     });
 }
@@ -768,25 +709,19 @@ int lsp_open_reduce(lsp_ctx* ctx, const lsp_fr* mat, size_t n, size_t w, const l
         const Fr* dm = dev_in(ctx, mat, n * w, mem, "api_in");
         const Fr* dinv = dev_in(ctx, inv_denoms, npoints * n, mem, "api_in2");
         Fr* dro = const_cast<Fr*>(dev_in(ctx, ro, n, mem, "api_out"));
-        // host side: alpha^c (c < w), per point the offset and offset * sum_c alpha^c y_c
-        const Fr A = to_fr(*alpha);
-        std::vector<Fr> apw(w), coef(2 * npoints);
-        Fr pw = fr_one();
-        for (size_t c = 0; c < w; ++c) {
-            apw[c] = pw;
-            pw = fr_mul(pw, A);
-        }
+        // host side: alpha^c (c < w), then per point the offset, then per point offset * sum_c alpha^c y_c
+        std::vector<Fr> coef = alpha_powers(to_fr(*alpha), w + 1);
+        const Fr aw = coef[w];  // alpha^w: the offset advances by the matrix width
+        coef.resize(w + 2 * npoints);
+        const std::vector<Fr> y = to_frs(ys, npoints * w);
         Fr off = to_fr(*alpha_pow_offset);
         for (size_t p = 0; p < npoints; ++p) {
-            Fr ry = fr_zero();
-            for (size_t c = 0; c < w; ++c) ry = fr_add(ry, fr_mul(apw[c], to_fr(ys[p * w + c])));
-            coef[p] = off;
-            coef[npoints + p] = fr_mul(off, ry);
-            off = fr_mul(off, pw);  // pw = alpha^w: the offset advances by the matrix width
+            coef[w + p] = off;
+            coef[w + npoints + p] = fr_mul(off, reduce_opened(coef.data(), y.data() + p * w, w));
+            off = fr_mul(off, aw);
         }
         Fr* dc = ctx->fbuf("api_coef", w + 2 * npoints);
-        LSP_HIP(hipMemcpyAsync(dc, apw.data(), w * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-        LSP_HIP(hipMemcpyAsync(dc + w, coef.data(), 2 * npoints * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+        ctx->h2d_async("api_coef_h", dc, coef.data(), coef.size() * sizeof(Fr));
         LSP_HIP(launch_reduce_matrix(dm, n, (uint32_t)w, dc, (uint32_t)npoints, dinv, dc + w, dc + w + npoints, dro,
                                      ctx->stream));
         finish_out(ctx, ro, dro, n, mem);
@@ -801,8 +736,7 @@ int lsp_prove(lsp_ctx* ctx, const lsp_fr* trace, size_t h, size_t w, const int32
         std::lock_guard<std::mutex> g(ctx->mu);
         need_gpu(ctx);
         const Air A = Air::parse(air, air_len);
-        std::vector<Fr> pub(npub);
-        for (size_t i = 0; i < npub; ++i) pub[i] = to_fr(pubv[i]);
+        const std::vector<Fr> pub = to_frs(pubv, npub);
         const Fr* din = dev_in(ctx, trace, h * w, mem, "trace_in");
         // the reference's debug-build check_constraints, opt-in (read per call, as LSP_QUOTIENT_ORDER is)
         if (const char* e = std::getenv("LSP_CHECK_CONSTRAINTS")) {
@@ -847,8 +781,7 @@ int lsp_check_constraints(lsp_ctx* ctx, const lsp_fr* trace, size_t h, size_t w,
         std::lock_guard<std::mutex> g(ctx->mu);
         const Air A = Air::parse(air, air_len);
         LSP_REQUIRE(A.max_col < w, LSP_E_ARG, "AIR column id outside the trace width");
-        std::vector<Fr> pub(npub);
-        for (size_t i = 0; i < npub; ++i) pub[i] = to_fr(pubv[i]);
+        const std::vector<Fr> pub = to_frs(pubv, npub);
         CheckReport r;
         if (ctx->device == LSP_HOST_ONLY && mem == LSP_MEM_HOST) {
             // the host twin: a host-only context checks host memory (never a fallback on a GPU context)
@@ -914,8 +847,7 @@ int lsp_prove_group(lsp_group* grp, const lsp_fr* const* traces, size_t h, size_
         LSP_REQUIRE(grp && traces && out && pubv, LSP_E_ARG, "bad prove_group arguments");
         const int G = (int)grp->ctxs.size();
         const Air A = Air::parse(air, air_len);
-        std::vector<Fr> pub(npub);
-        for (size_t i = 0; i < npub; ++i) pub[i] = to_fr(pubv[i]);
+        const std::vector<Fr> pub = to_frs(pubv, npub);
         ThreadGroup tg(G);
         for (int r = 0; r < G; ++r) tg.device[r] = grp->ctxs[r]->device;
         std::vector<lsp_proof*> res(G, nullptr);
@@ -1159,8 +1091,7 @@ int lsp_prove_sharded(lsp_ctx* ctx, const lsp_fr* trace, size_t h, size_t w, con
         LSP_REQUIRE(ctx->comm, LSP_E_STATE, "no communicator attached (lsp_ctx_attach_*)");
         need_gpu(ctx);
         const Air A = Air::parse(air, air_len);
-        std::vector<Fr> pub(npub);
-        for (size_t i = 0; i < npub; ++i) pub[i] = to_fr(pubv[i]);
+        const std::vector<Fr> pub = to_frs(pubv, npub);
         const Fr* din = dev_in(ctx, trace, h * w, mem, "trace_in");
         *out = prove_shard(ctx, *ctx->comm, din, h, w, A, pub.data(), npub);
     });
@@ -1217,8 +1148,7 @@ int lsp_verify(const lsp_ctx* ctx, const int32_t* air, size_t air_len, const lsp
     int g = guarded(nullptr, [&] {
         LSP_REQUIRE(ctx && pubv && proof, LSP_E_ARG, "bad verify arguments");
         const Air A = Air::parse(air, air_len);
-        std::vector<Fr> pub(npub);
-        for (size_t i = 0; i < npub; ++i) pub[i] = to_fr(pubv[i]);
+        const std::vector<Fr> pub = to_frs(pubv, npub);
         const int v = verify_host(ctx, A, pub.data(), npub, proof, len);
         if (v != 0) {
             g_err = "proof rejected at check " + std::to_string(v);
@@ -1265,17 +1195,8 @@ int lsp_calibrate_fr_mul(lsp_ctx* ctx, double* gmul_per_s) {
         const uint32_t iters = 256;
         Fr* out = ctx->fbuf("calib", nth);
         LSP_HIP(launch_calib_mul(out, nth, 8, ctx->stream));  // warm
-        hipEvent_t e0, e1;
-        LSP_HIP(hipEventCreate(&e0));
-        LSP_HIP(hipEventCreate(&e1));
-        LSP_HIP(hipEventRecord(e0, ctx->stream));
-        LSP_HIP(launch_calib_mul(out, nth, iters, ctx->stream));
-        LSP_HIP(hipEventRecord(e1, ctx->stream));
-        LSP_HIP(hipEventSynchronize(e1));
-        float ms = 0;
-        LSP_HIP(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
+        StreamTimer timer;
+        const float ms = timer.ms(ctx->stream, [&] { LSP_HIP(launch_calib_mul(out, nth, iters, ctx->stream)); });
         *gmul_per_s = (double)nth * iters * 4 / (ms * 1e-3) / 1e9;
     });
 }
@@ -1437,22 +1358,15 @@ int lsp_calibrate_poseidon2(lsp_ctx* ctx, double* mperm_per_s) {
         const uint32_t iters = 4;
         Fr* out = ctx->fbuf("calib", (size_t)256 * 256 * 32);
         LSP_HIP(launch_calib_perm(out, (size_t)256 * 256 * 4, 1, ctx->rc29_dev, ctx->p2.L, ctx->stream));  // warm
-        hipEvent_t e0, e1;
-        LSP_HIP(hipEventCreate(&e0));
-        LSP_HIP(hipEventCreate(&e1));
+        StreamTimer timer;
         double best = 0;
         for (size_t per_cu : {2, 4, 8, 16, 32}) {
             const size_t nth = (size_t)256 * 256 * per_cu;
-            LSP_HIP(hipEventRecord(e0, ctx->stream));
-            LSP_HIP(launch_calib_perm(out, nth, iters, ctx->rc29_dev, ctx->p2.L, ctx->stream));
-            LSP_HIP(hipEventRecord(e1, ctx->stream));
-            LSP_HIP(hipEventSynchronize(e1));
-            float ms = 0;
-            LSP_HIP(hipEventElapsedTime(&ms, e0, e1));
+            const float ms = timer.ms(ctx->stream, [&] {
+                LSP_HIP(launch_calib_perm(out, nth, iters, ctx->rc29_dev, ctx->p2.L, ctx->stream));
+            });
             best = std::max(best, (double)nth * iters / (ms * 1e-3) / 1e6);
         }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
         *mperm_per_s = best;
     });
 }

@@ -86,24 +86,17 @@ double calibrate_intt(lsp_ctx* ctx, uint32_t log_h, size_t w, int reps, const st
     // own phase at 2^20 x 4 (tests/test_gpu_calibration.py)
     constexpr int burst = 8;
     auto inv = [&] { LSP_HIP(launch_intt(x, ColMap::plain((uint32_t)w), y, w, log_h, tw, ctx->stream)); };
-    hipEvent_t e0, e1;
-    LSP_HIP(hipEventCreate(&e0));
-    LSP_HIP(hipEventCreate(&e1));
+    StreamTimer timer;
     std::vector<double> t;
     for (int r = 0; r <= reps; ++r) {
         if (before) before();
         if (!r)
             for (int i = 0; i < burst; ++i) inv();  // warm-up burst
-        LSP_HIP(hipEventRecord(e0, ctx->stream));
-        for (int i = 0; i < burst; ++i) inv();
-        LSP_HIP(hipEventRecord(e1, ctx->stream));
-        LSP_HIP(hipEventSynchronize(e1));
-        float ms = 0;
-        LSP_HIP(hipEventElapsedTime(&ms, e0, e1));
+        const float ms = timer.ms(ctx->stream, [&] {
+            for (int i = 0; i < burst; ++i) inv();
+        });
         if (r) t.push_back(ms / burst);
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     std::sort(t.begin(), t.end());
     return (double)(h * w) / (t[t.size() / 2] * 1e-3) / 1e9;
 }

@@ -53,6 +53,38 @@ void dbg_check_after(const char* what);  // (inside namespace lsp)
         if (!(cond)) throw ::lsp::LspError((code), (msg));    \
     } while (0)
 
+// Device time of work issued to a stream: ms(st, f) records an event, calls f
+// (which enqueues on st), records another, waits for it and returns the
+// milliseconds between the two.  The events live as long as the timer and are
+// destroyed on every path out, a throwing f included.
+struct StreamTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    StreamTimer() {
+        LSP_HIP(hipEventCreate(&e0));
+        const hipError_t e = hipEventCreate(&e1);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(e0);
+            LSP_HIP(e);
+        }
+    }
+    StreamTimer(const StreamTimer&) = delete;
+    StreamTimer& operator=(const StreamTimer&) = delete;
+    ~StreamTimer() {
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    }
+    template <class F>
+    float ms(hipStream_t st, F&& f) {
+        LSP_HIP(hipEventRecord(e0, st));
+        f();
+        LSP_HIP(hipEventRecord(e1, st));
+        LSP_HIP(hipEventSynchronize(e1));
+        float t = 0;
+        LSP_HIP(hipEventElapsedTime(&t, e0, e1));
+        return t;
+    }
+};
+
 inline Fr to_fr(const lsp_fr& x) {
     Fr r;
     for (int i = 0; i < 4; ++i) {

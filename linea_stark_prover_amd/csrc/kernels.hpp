@@ -93,6 +93,13 @@ struct MatList {
     uint32_t width[8];
     uint32_t n;
 };
+inline MatList one_mat(const Fr* p, uint32_t w) {
+    MatList m{};
+    m.ptr[0] = p;
+    m.width[0] = w;
+    m.n = 1;
+    return m;
+}
 // round constants (ark form) -> the 29-bit-limb form the permutation kernels take
 hipError_t launch_rc_to_f29(const Fr* rc, F29* rc29, uint32_t n, hipStream_t st);
 hipError_t launch_permute(Fr* states, size_t n, const F29* rc29, P2Layout L, hipStream_t st);

@@ -100,14 +100,6 @@ void resolve_timings(lsp_ctx* ctx) {
     ctx->pending_timings.clear();
 }
 
-static MatList one_mat(const Fr* p, uint32_t w) {
-    MatList m{};
-    m.ptr[0] = p;
-    m.width[0] = w;
-    m.n = 1;
-    return m;
-}
-
 // --------------------------------------------------------------- grind
 // GrindingChallenger::grind(bits) on the device: the smallest witness w >= 0
 // with sample_bits(bits) == 0 after observe(w) (U8).  The sponge over the
@@ -376,8 +368,6 @@ struct Prover {
     void quotient_setup() {
         const size_t h = s.h, w = s.w, q = s.q, S = s.S, Q = s.Q, Sq = s.Sq, Gq = s.Gq;
         const uint32_t G = s.G, g = s.g;
-        uint32_t L1Q;
-        const Fr* tabQ = pow_table(ctx, "tabQ", host_two_adic_generator(s.logQ), s.logQ, L1Q);
         qv = G == 1 || !s.qsplit ? ctx->fbuf("q_values", Q) : nullptr;
         stage = G == 1 ? nullptr : ctx->fbuf("q_stage", Sq * Gq);
         qloc = G == 1 ? qv
@@ -397,56 +387,11 @@ struct Prover {
             }
         }
         if (s.row0 >= Q) return;
-        const uint64_t i0 = host_bitrev(g, s.logGq);
-        // 1/((x-1)(x-w_h^-1)) depends on the domain only: cached per shape in the context
-        char key[64];
-        std::snprintf(key, sizeof key, "qsel_%u_%u_%llu_%u", s.log_h, s.logQ, (unsigned long long)i0, s.logGq);
-        Fr* inv_den;
-        auto it = ctx->ptabs.find(key);
-        if (it != ctx->ptabs.end()) {
-            inv_den = const_cast<Fr*>(it->second);
-        } else {
-            Fr* den = ctx->fbuf("q_den", Sq);
-            inv_den = ctx->fbuf(key, Sq);
-            LSP_HIP(launch_selector_denoms(tabQ, L1Q, GEN, wh_inv, Sq, den, st, i0, s.logGq));
-            LSP_HIP(launch_batch_inverse(den, inv_den, Sq, st, ctx->bi_scratch(Sq)));
-            ctx->ptabs[key] = inv_den;
-        }
-        std::vector<Fr> zh(q), izh(q);
-        {
-            const Fr gh = fr_pow_u64(GEN, h), gq = host_two_adic_generator(s.log_q);
-            Fr x = one;
-            for (size_t k = 0; k < q; ++k) {
-                zh[k] = fr_sub(fr_mul(gh, x), one);
-                izh[k] = host_inv_cached(zh[k]);
-                x = fr_mul(x, gq);
-            }
-        }
-        Fr* dzh = ctx->fbuf("q_zh", 2 * q);
-        zh.insert(zh.end(), izh.begin(), izh.end());
-        ctx->h2d_async("q_zh_h", dzh, zh.data(), 2 * q * sizeof(Fr));
-        int32_t* dair = (int32_t*)ctx->buf("air", air.raw.size() * sizeof(int32_t));
-        ctx->h2d_async("air_h", dair, air.raw.data(), air.raw.size() * sizeof(int32_t));
+        quotient_domain(ctx, s.log_h, s.log_q, host_bitrev(g, s.logGq), s.logGq, Sq, air, pub[0], pub[1], qa);
         qa.lde = lde;
         qa.w = (uint32_t)w;
-        qa.logQ = s.logQ;
-        qa.log_q = s.log_q;
-        qa.air = dair;
-        qa.air_len = (uint32_t)air.raw.size();
-        qa.pub_alpha = pub[0];
-        qa.pub_delta = pub[1];
-        qa.gen = GEN;
-        qa.wh_inv = wh_inv;
-        qa.tabQ = tabQ;
-        qa.L1 = L1Q;
-        qa.zh = dzh;
-        qa.inv_zh = dzh + q;
-        qa.inv_den = inv_den;
         qa.out = qloc;
-        qa.i0 = i0;
-        qa.log_step = s.logGq;
         qa.row0 = s.row0;
-        qa.n = Sq;
         qa.lde_next = lde_next;
         qa.row0_next = row0_next;
         qa.lde_rows = S;
@@ -550,8 +495,7 @@ struct Prover {
         const uint32_t G = s.G, g = s.g, logN = s.logN;
         const Fr zeta_next = fr_mul(zeta, wh);
         T.begin("open");
-        uint32_t L1N;
-        const Fr* tabN = inverse_denominators(zeta, zeta_next, L1N);
+        inverse_denominators(zeta, zeta_next);
         T.begin("compute opened values with Lagrange interpolation");
         // Barycentric sums over one coset c H_h of the LDE domain: p(z) =
         // (z^h - c^h) / (h c^h) * sum_i p(x_i) x_i / (z - x_i).  Any coset gives
@@ -574,16 +518,12 @@ struct Prover {
                 job_here[j] = g == (nfree ? G - 1 - (uint32_t)j % nfree : G - 1 - (uint32_t)j % G);
         }
         if (job_here[0] || job_here[1] || job_here[2]) {
-            Fr* partial = ctx->fbuf("o_partial", ((nlow + 1023) / 1024) * maxw);
+            ctx->fbuf("o_partial", ((nlow + 1023) / 1024) * maxw);  // the drivers' scratch, sized once for the widest job
             const Fr* jm[3] = {lde, lde, qlde};
             const Fr* jinv[3] = {inv_z, inv_zn, inv_z};
-            for (int j = 0; j < 3; ++j) {
-                if (!job_here[j]) continue;
-                uint32_t nb = 0;
-                LSP_HIP(launch_interp_partial(jm[j], (uint32_t)jw[j], nlow, jinv[j], GEN, tabN, L1N, logN, partial, &nb,
-                                              st, row0));
-                LSP_HIP(launch_sum_partials(partial, nb, (uint32_t)jw[j], sums + joff[j], st));
-            }
+            for (int j = 0; j < 3; ++j)
+                if (job_here[j])
+                    barycentric_sums(ctx, jm[j], (uint32_t)jw[j], nlow, jinv[j], GEN, logN, row0, sums + joff[j]);
         }
         Fr* hs = (Fr*)ctx->hbuf("o_sums_h", nsum * sizeof(Fr));  // pinned
         if (job_here[0] || job_here[1] || job_here[2]) {
@@ -592,12 +532,10 @@ struct Prover {
         }
         // the coset of this rank's first rows: c = GEN w_N^bitrev(row0) (sub: the low coset, GEN)
         const Fr cpos = s.sub ? GEN : fr_mul(GEN, fr_pow_u64(host_two_adic_generator(logN), host_bitrev(row0, logN)));
-        const Fr ch_ = fr_pow_u64(cpos, h);
-        const Fr dinv = host_inv_cached(fr_mul(ch_, fr_from_u64(h)));
-        auto factor = [&](const Fr& z) { return fr_mul(fr_sub(fr_pow_u64(z, h), ch_), dinv); };
+        const CosetFactor factor(cpos, h, true);
         const Fr jz[3] = {zeta, zeta_next, zeta};
         for (int j = 0; j < 3; ++j) {
-            const Fr f = factor(jz[j]);
+            const Fr f = factor.at(jz[j]);
             for (size_t k = 0; k < jw[j]; ++k) hs[joff[j] + k] = job_here[j] ? fr_mul(hs[joff[j] + k], f) : fr_zero();
         }
         if (G > 1) {  // every value from its job's rank(s): the sum over ranks
@@ -614,16 +552,13 @@ struct Prover {
         T.end("compute opened values with Lagrange interpolation");
     }
 
-    // inv_z, inv_zn over this rank's rows; returns the LDE domain's power table
-    const Fr* inverse_denominators(const Fr& zeta, const Fr& zeta_next, uint32_t& L1N) {
+    // inv_z, inv_zn over this rank's rows
+    void inverse_denominators(const Fr& zeta, const Fr& zeta_next) {
         const size_t S = s.S, row0 = s.row0;
         const uint32_t logN = s.logN;
         T.begin("compute_inverse_denominators");
-        const Fr* tabN = pow_table(ctx, "tabN", host_two_adic_generator(logN), logN, L1N);
-        Fr* dtmp = ctx->fbuf("o_den", S);
         inv_z = ctx->fbuf("o_invz", S);
         inv_zn = ctx->fbuf("o_invzn", S);
-        LSP_HIP(launch_open_denoms(zeta, GEN, tabN, L1N, logN, S, dtmp, st, row0));
         // this rank's rows are the coset c H_S (c = GEN w_N^bitrev(row0)), so the
         // product of its denominators is prod (zeta - c w) = zeta^S - c^S: its
         // inverse on the host replaces the batch inverse's Fermat chain on the GPU
@@ -631,20 +566,18 @@ struct Prover {
         const Fr den_prod = fr_sub(fr_pow_u64(zeta, S), cS);
         LSP_REQUIRE(!fr_is_zero(den_prod), LSP_E_STATE, "zeta lies in the LDE domain");
         const Fr den_prod_inv = fr_inv(den_prod);
-        LSP_HIP(launch_batch_inverse(dtmp, inv_z, S, st, ctx->bi_scratch(S), &den_prod_inv));
+        open_denominators(ctx, zeta, GEN, logN, row0, S, inv_z, &den_prod_inv);
         if (s.sub) {
             // x w_h^-1 leaves a sub-coset (w_h is not in H_S): the zeta_next
             // denominators are inverted on their own
             const Fr dpn = fr_sub(fr_pow_u64(zeta_next, S), cS);
             LSP_REQUIRE(!fr_is_zero(dpn), LSP_E_STATE, "zeta * w_h lies in the LDE domain");
             const Fr dpn_inv = fr_inv(dpn);
-            LSP_HIP(launch_open_denoms(zeta_next, GEN, tabN, L1N, logN, S, dtmp, st, row0));
-            LSP_HIP(launch_batch_inverse(dtmp, inv_zn, S, st, ctx->bi_scratch(S), &dpn_inv));
+            open_denominators(ctx, zeta_next, GEN, logN, row0, S, inv_zn, &dpn_inv);
         } else {
             LSP_HIP(launch_shift_inverse(inv_z, inv_zn, wh_inv, logN, 1ull << s.lb, row0, S, st));
         }
         T.end("compute_inverse_denominators");
-        return tabN;
     }
 
     // the first FRI vector: every opened matrix reduced by powers of alpha_fri
@@ -657,14 +590,9 @@ struct Prover {
         span("reduce matrix quotient", w, s.N, -1);
         span("reduce matrix quotient", w, s.N, -1);
         for (size_t j = 0; j < q; ++j) span("reduce matrix quotient", 1, s.N, -1);
-        std::vector<Fr> apw(2 * w + q);
-        apw[0] = one;
-        for (size_t k = 1; k < apw.size(); ++k) apw[k] = fr_mul(apw[k - 1], alpha_fri);
-        Fr ry_z = fr_zero(), ry_zn = fr_zero();
-        for (size_t c = 0; c < w; ++c) {
-            ry_z = fr_add(ry_z, fr_mul(apw[c], proof->tl[c]));
-            ry_zn = fr_add(ry_zn, fr_mul(apw[c], proof->tn[c]));
-        }
+        std::vector<Fr> apw = alpha_powers(alpha_fri, 2 * w + q);
+        const Fr ry_z = reduce_opened(apw.data(), proof->tl.data(), w);
+        const Fr ry_zn = reduce_opened(apw.data(), proof->tn.data(), w);
         Fr* dapw = ctx->fbuf("o_apw", apw.size() + q);
         const size_t napw = apw.size();
         apw.insert(apw.end(), proof->qc.begin(), proof->qc.end());
@@ -744,8 +672,7 @@ struct Prover {
 
     void flush_fold() {  // the fold no later leaf kernel will run
         if (!pending) return;
-        LSP_HIP(launch_fri_fold(pend.v, pend_m, pend.half, pend.half_beta, pend.tab, pend.L1, pend.vout, st, pend.i0,
-                                (int)pend.logm));
+        fri_fold(ctx, pend, pend_m);
         pending = false;
     }
 
@@ -764,18 +691,9 @@ struct Prover {
         proof->roots.push_back(root);
         ch.observe(root);
         const Fr beta = ch.sample();
-        uint32_t L1F;
-        const uint32_t logm = log2_exact(m);
-        const Fr ginv = host_inv_cached(host_two_adic_generator(logm + 1));
-        const Fr* tabF = pow_table(ctx, "tabF", ginv, logm, L1F);
+        pend = fold_spec(ctx, log2_exact(m), sharded ? (uint64_t)s.g * ml : 0, beta);
         pend.v = fv + vo;
         pend.vout = fv + vo + 2 * ml;
-        pend.half = half;
-        pend.half_beta = fr_mul(beta, half);
-        pend.tab = tabF;
-        pend.L1 = L1F;
-        pend.logm = logm;
-        pend.i0 = sharded ? (uint64_t)s.g * ml : 0;
         pend_m = ml;
         pending = true;
         rounds.push_back(std::move(R));

@@ -25,6 +25,38 @@ void lde_coeffs_device(lsp_ctx* ctx, const Fr* coef, ColMap map, size_t h, size_
 // block `blk` (N / 2^b < h rows) of the N-row LDE, folded from the coefficients; buffers named after `tag`
 void subcoset_lde(lsp_ctx* ctx, const Fr* coef, ColMap map, size_t h, size_t w, uint32_t logN, uint32_t b,
                   uint32_t blk, const Fr* shifts_host, Fr* d_out, const std::string& tag);
+// ---- stages.cpp: one driver per proof stage, shared by the Prover's phases and the C stage API
+// The quotient domain of a 2^log_h-row trace with 2^log_q chunks, for the
+// points i = i0 + (m << log_step), m < n (one residue class; n = 0: all of it):
+// fills every field of `qa` that depends neither on alpha nor on where the LDE
+// rows live (logQ, log_q, air, air_len, pub_*, gen, wh_inv, tabQ, L1, zh,
+// inv_zh, inv_den, i0, log_step, n).  Owns the context's "qsel_*" cache of
+// inverted selector denominators.
+void quotient_domain(lsp_ctx* ctx, uint32_t log_h, uint32_t log_q, uint64_t i0, uint32_t log_step, size_t n,
+                     const Air& air, const Fr& pub_alpha, const Fr& pub_delta, QuotientArgs& qa);
+// out[i] = 1 / (z - shift w_N^bitrev(row0 + i)), i < n.  inv_total (optional):
+// 1 / (the product of the n denominators) where the caller knows it in closed form
+void open_denominators(lsp_ctx* ctx, const Fr& z, const Fr& shift, uint32_t logN, uint64_t row0, size_t n, Fr* out,
+                       const Fr* inv_total = nullptr);
+// Barycentric interpolation over a coset c H_h: p(z) = factor(z) * sum_i p(x_i) x_i / (z - x_i).
+// sums[c] = sum_{i < n} M[i][c] x_i inv_den[i], x_i = shift w_N^bitrev(row0 + i), for the n x w matrix M
+void barycentric_sums(lsp_ctx* ctx, const Fr* M, uint32_t w, size_t n, const Fr* inv_den, const Fr& shift,
+                      uint32_t logN, uint64_t row0, Fr* sums);
+// factor(z) = (z^h - c^h) / (h c^h); domain_constant: c is one (its inverse goes through host_inv_cached)
+struct CosetFactor {
+    size_t h;
+    Fr ch, inv_hch;
+    CosetFactor(const Fr& c, size_t h, bool domain_constant);
+    Fr at(const Fr& z) const { return fr_mul(fr_sub(fr_pow_u64(z, h), ch), inv_hch); }
+};
+// the FRI fold by beta of a vector of global folded length 2^logm, for the
+// pairs from global pair index i0 on (v and vout are the caller's to set);
+// fri_fold launches it for m pairs
+FoldSpec fold_spec(lsp_ctx* ctx, uint32_t logm, uint64_t i0, const Fr& beta);
+void fri_fold(lsp_ctx* ctx, const FoldSpec& f, size_t m);
+// alpha^k, k < n, and a row of opened values reduced by them: sum_c apw[c] ys[c], c < w
+std::vector<Fr> alpha_powers(const Fr& alpha, size_t n);
+Fr reduce_opened(const Fr* apw, const Fr* ys, size_t w);
 // ---- merkle.cpp
 // one per proof in flight, for the proof's whole duration (the tree tops share the host's cores)
 struct ActiveProof {
