@@ -59,8 +59,31 @@ enum { LSP_MEM_HOST = 0, LSP_MEM_DEVICE = 1 };
  *   2, na, a_ids[na], ntables, ncols, b_ids[ntables*ncols], a_filter_id,
  *   b_filter_ids[ntables], a_inverses_id, b_inverses_ids[ntables],
  *   occurrences_ids[ntables], check_id
- * Column ids are absolute (already shifted, trace/src/lib.rs:40-58). */
-enum { LSP_AIR_PERMUTATION = 1, LSP_AIR_LOOKUP = 2 };
+ * Column ids are absolute (already shifted, trace/src/lib.rs:40-58).
+ * LSP_AIR_PROGRAM: a straight-line program over field registers ("slots"),
+ * the shape of p3-uni-stark's SymbolicExpression, for an AIR of the caller's:
+ *   3, width, nslots, nconst, nops, nassert,
+ *   const[nconst][8]   canonical value < r, eight little-endian 32-bit words
+ *                      (as int32 bit patterns)
+ *   op[nops][4]        opcode, dst, a, b
+ * Opcodes: 1 ADD, 2 SUB, 3 MUL: slot dst = a op b.  4 ASSERT_ZERO: a is the
+ * next constraint's value (dst = b = 0).  A negation is SUB(const 0, x).
+ * An operand is kind << 24 | payload:
+ *   0 SLOT s     1 LOCAL col     2 NEXT col     3 PUBLIC k     4 CONST i
+ *   5 IS_FIRST_ROW     6 IS_LAST_ROW     7 IS_TRANSITION     (payload 0)
+ * The selectors are the values the evaluation is handed -- Z_H/(x - 1),
+ * Z_H/(x - w^-1) and x - w^-1 on the quotient domain and at zeta, 0/1 in
+ * lsp_check_constraints -- and may stand anywhere in an expression.
+ * Limits (LSP_E_ARG, the message names the op): nslots <= 16, nconst <= 2^16,
+ * 1 <= nops <= 2^20, nassert = the number of ASSERT_ZERO ops >= 1, columns
+ * < width <= 2^20, public indices < 2^16, every slot written before it is
+ * read, no unknown opcode or kind, unused fields zero.  Where the trace width
+ * and the public values are known (prove, verify, check, quotient) a column
+ * >= w or a PUBLIC k >= npub is LSP_E_ARG too.  Public values stay
+ * [alpha, delta, ...]: the built-in configs read the first two, programs any.
+ * A descriptor may mix the three types; constraints are numbered and folded
+ * in descriptor order, a program's in the order of its ASSERT_ZERO ops. */
+enum { LSP_AIR_PERMUTATION = 1, LSP_AIR_LOOKUP = 2, LSP_AIR_PROGRAM = 3 };
 
 typedef struct lsp_ctx lsp_ctx;
 typedef struct lsp_tree lsp_tree;
@@ -254,11 +277,18 @@ enum {
     LSP_CONSTRAINT_A_INVERSE = 1, /* lookup: a_chal * a_inverses - 1 */
     LSP_CONSTRAINT_FIRST_ROW = 2, /* when_first_row: the check column's first value */
     LSP_CONSTRAINT_TRANSITION = 3, /* when_transition: the check column's recurrence */
-    LSP_CONSTRAINT_LAST_ROW = 4   /* when_last_row: the check column's last value */
+    LSP_CONSTRAINT_LAST_ROW = 4,  /* when_last_row: the check column's last value */
+    LSP_CONSTRAINT_PROGRAM = 5    /* an ASSERT_ZERO of an LSP_AIR_PROGRAM config */
 };
 /* number of constraints LineaAIR::eval emits for this descriptor:
- * 4 per permutation config, 4 + ntables per lookup config */
+ * 4 per permutation config, 4 + ntables per lookup config, nassert per program */
 int lsp_air_num_constraints(const int32_t *air, size_t air_len, uint32_t *n);
+/* degree of constraint j under p3-uni-stark's degree_multiple rule with
+ * public values counted as `public_degree` (lsp_params): the largest of them
+ * decides lsp_log_quotient_degree, so when a prove call answers "quotient
+ * degree exceeds the blowup" this names the constraint that does it.
+ * LSP_E_ARG when j is past the end. */
+int lsp_air_constraint_degree(const int32_t *air, size_t air_len, int32_t public_degree, uint32_t j, uint32_t *degree);
 /* constraint j -> its config's index and type (LSP_AIR_*), its kind
  * (LSP_CONSTRAINT_*) and, for a lookup's b_inverse constraint, the table
  * (-1 otherwise).  Any output may be NULL; LSP_E_ARG when j is past the end. */
@@ -278,8 +308,8 @@ typedef struct { uint64_t row; uint32_t constraint, reserved; lsp_fr value; } ls
  * the lowest of them (UINT64_MAX: none).  list: the first `cap` violations in
  * (row, constraint) order, nullable with cap = 0; *nlist (nullable when
  * cap = 0) = how many were written.  LSP_E_ARG: a NULL argument, fewer than
- * two public values, a bad descriptor, a column id >= w, or a height that is
- * no power of two.  On a GPU context one kernel reads the trace once (thread
+ * two public values, a bad descriptor, a column id >= w, a program's PUBLIC k
+ * >= npub, or a height that is no power of two.  On a GPU context one kernel reads the trace once (thread
  * i checks row i) and device memory beyond the trace is h/8 + O(ncons +
  * cap * ncons) bytes of the context's pool; a host-only context
  * (LSP_HOST_ONLY) checks host memory with a plain loop over the rows -- the

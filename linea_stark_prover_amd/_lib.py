@@ -14,9 +14,9 @@ LIB_PATH = os.environ.get("LSP_LIB", os.path.join(_PKG, "_lib", "liblsp_hip.so")
 
 LSP_OK, LSP_E_ARG, LSP_E_OOM, LSP_E_HIP, LSP_E_SIZE, LSP_E_VERIFY, LSP_E_STATE, LSP_E_CONSTRAINT = range(8)
 LSP_MEM_HOST, LSP_MEM_DEVICE = 0, 1
-LSP_AIR_PERMUTATION, LSP_AIR_LOOKUP = 1, 2
+LSP_AIR_PERMUTATION, LSP_AIR_LOOKUP, LSP_AIR_PROGRAM = 1, 2, 3
 (LSP_CONSTRAINT_B_INVERSE, LSP_CONSTRAINT_A_INVERSE, LSP_CONSTRAINT_FIRST_ROW, LSP_CONSTRAINT_TRANSITION,
- LSP_CONSTRAINT_LAST_ROW) = range(5)
+ LSP_CONSTRAINT_LAST_ROW, LSP_CONSTRAINT_PROGRAM) = range(6)
 
 c_fr_p = ctypes.c_void_p  # lsp_fr* (32-byte elements)
 
@@ -128,6 +128,8 @@ _SIGS = {
                                  ctypes.c_size_t, c_fr_p, ctypes.c_size_t, ctypes.c_int,
                                  ctypes.POINTER(ctypes.c_void_p)]),
     "lsp_air_num_constraints": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)]),
+    "lsp_air_constraint_degree": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_uint32,
+                                                 ctypes.POINTER(ctypes.c_uint32)]),
     "lsp_air_constraint_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,
                                                ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32),
                                                ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),

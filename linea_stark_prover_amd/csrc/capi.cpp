@@ -611,15 +611,16 @@ int lsp_quotient_values(lsp_ctx* ctx, const lsp_fr* lde, size_t h, size_t w, con
         std::lock_guard<std::mutex> g(ctx->mu);
         need_gpu(ctx);
         const Air A = Air::parse(air, air_len);
-        LSP_REQUIRE(A.max_col < w, LSP_E_ARG, "AIR column outside width");
+        A.require_fits(w, npub);
         const uint32_t log_h = log2_exact(h), log_q = A.log_quotient_degree(ctx->public_degree);
         const uint32_t logQ = log_h + log_q;
-        LSP_REQUIRE(log_q <= ctx->log_blowup, LSP_E_ARG, "quotient degree exceeds blowup");
+        LSP_REQUIRE(log_q <= ctx->log_blowup, LSP_E_ARG, "quotient degree exceeds the blowup");
         const size_t N = h << ctx->log_blowup, Q = (size_t)1 << logQ;
         const Fr* dlde = dev_in(ctx, lde, N * w, mem, "api_in");
         Fr* dout = dev_out(ctx, out, Q, mem, "api_out");
         QuotientArgs qa;
-        quotient_domain(ctx, log_h, log_q, 0, 0, Q, A, to_fr(pubv[0]), to_fr(pubv[1]), qa);
+        const std::vector<Fr> pub = to_frs(pubv, npub);
+        quotient_domain(ctx, log_h, log_q, 0, 0, Q, A, pub.data(), npub, qa);
         qa.lde = dlde;
         qa.w = (uint32_t)w;
         qa.alpha = to_fr(*alpha);
@@ -757,6 +758,17 @@ int lsp_air_num_constraints(const int32_t* air, size_t air_len, uint32_t* n) {
     });
 }
 
+int lsp_air_constraint_degree(const int32_t* air, size_t air_len, int32_t public_degree, uint32_t j,
+                              uint32_t* degree) {
+    return guarded(nullptr, [&] {
+        LSP_REQUIRE(degree, LSP_E_ARG, "null");
+        LSP_REQUIRE(public_degree >= 0 && public_degree <= 1024, LSP_E_ARG, "public_degree outside [0, 1024]");
+        const std::vector<int> d = Air::parse(air, air_len).degrees(public_degree);
+        LSP_REQUIRE(j < d.size(), LSP_E_ARG, "constraint index past the AIR's last constraint");
+        *degree = (uint32_t)d[j];
+    });
+}
+
 int lsp_air_constraint_info(const int32_t* air, size_t air_len, uint32_t j, uint32_t* config, int32_t* type,
                             int32_t* kind, int32_t* table) {
     return guarded(nullptr, [&] {
@@ -780,7 +792,7 @@ int lsp_check_constraints(lsp_ctx* ctx, const lsp_fr* trace, size_t h, size_t w,
         LSP_REQUIRE(h && !(h & (h - 1)), LSP_E_ARG, "trace height must be a power of two");
         std::lock_guard<std::mutex> g(ctx->mu);
         const Air A = Air::parse(air, air_len);
-        LSP_REQUIRE(A.max_col < w, LSP_E_ARG, "AIR column id outside the trace width");
+        A.require_fits(w, npub);
         const std::vector<Fr> pub = to_frs(pubv, npub);
         CheckReport r;
         if (ctx->device == LSP_HOST_ONLY && mem == LSP_MEM_HOST) {

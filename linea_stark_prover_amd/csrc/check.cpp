@@ -22,8 +22,7 @@ void summarise(CheckReport& r) {
 }
 
 void check_shape(size_t h, size_t w, const Air& air, size_t npub) {
-    LSP_REQUIRE(npub >= 2, LSP_E_ARG, "public values must hold [alpha, delta]");
-    LSP_REQUIRE(air.max_col < w, LSP_E_ARG, "AIR column id outside the trace width");
+    air.require_fits(w, npub);
     (void)log2_exact(h);
 }
 }  // namespace
@@ -44,7 +43,7 @@ CheckReport check_constraints_host(const Fr* trace, size_t h, size_t w, const Ai
         const bool last = i + 1 == h;
         uint32_t j = 0;
         bool any = false;
-        air.eval(loc, nxt, pub[0], pub[1], i == 0 ? one : zero, last ? one : zero, last ? zero : one,
+        air.eval(loc, nxt, pub, i == 0 ? one : zero, last ? one : zero, last ? zero : one,
                  [&](const Fr& x) {
                      vals[j] = x;
                      if (!fr_is_zero(x)) {
@@ -72,8 +71,8 @@ CheckReport check_constraints_device(lsp_ctx* ctx, const Fr* d_trace, size_t h, 
     const size_t nwords = (h + 63) / 64;
     uint64_t* mask = (uint64_t*)ctx->buf("chk_mask", nwords * sizeof(uint64_t));
     uint64_t* cnt = (uint64_t*)ctx->buf("chk_count", 2 * (size_t)nc * sizeof(uint64_t));
-    int32_t* dair = (int32_t*)ctx->buf("chk_air", air.raw.size() * sizeof(int32_t));
-    LSP_HIP(hipMemcpyAsync(dair, air.raw.data(), air.raw.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+    int32_t* dair = (int32_t*)ctx->buf("chk_air", air.dev.size() * sizeof(int32_t));
+    LSP_HIP(hipMemcpyAsync(dair, air.dev.data(), air.dev.size() * sizeof(int32_t), hipMemcpyHostToDevice,
                            ctx->stream));
     LSP_HIP(hipMemsetAsync(mask, 0, nwords * sizeof(uint64_t), ctx->stream));
     LSP_HIP(hipMemsetAsync(cnt, 0, (size_t)nc * sizeof(uint64_t), ctx->stream));
@@ -86,6 +85,14 @@ CheckReport check_constraints_device(lsp_ctx* ctx, const Fr* d_trace, size_t h, 
     a.ncons = nc;
     a.pub_alpha = pub[0];
     a.pub_delta = pub[1];
+    if (air.has_prog) {  // (pub outlives the copy: the ctx->sync() below)
+        Fr* dpub = ctx->fbuf("chk_pub", npub);
+        LSP_HIP(hipMemcpyAsync(dpub, pub, npub * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+        a.pub = dpub;
+        a.npub = (uint32_t)npub;
+        a.prog = 1;
+        a.prog_slots = air.prog_slots;
+    }
     a.row_mask = mask;
     a.count = cnt;
     a.first_row = cnt + nc;
@@ -129,6 +136,7 @@ static const char* kind_name(int32_t kind) {
         case LSP_CONSTRAINT_A_INVERSE: return "a_inverse";
         case LSP_CONSTRAINT_FIRST_ROW: return "first_row";
         case LSP_CONSTRAINT_TRANSITION: return "transition";
+        case LSP_CONSTRAINT_PROGRAM: return "program assert";
         default: return "last_row";
     }
 }

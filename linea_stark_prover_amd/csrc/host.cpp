@@ -186,6 +186,86 @@ Fr P2Host::hash(const Fr* in, size_t n) const {
 }
 
 // ------------------------------------------------------------------- AIR
+// An LSP_AIR_PROGRAM config (include/lsp.h) after its type word.  Everything a
+// kernel later indexes with -- slots, constants, columns, public values -- is
+// checked here or in require_fits, and a slot is read only after an earlier op
+// wrote it, so no evaluator ever sees an undefined register.
+template <class Next>
+static void parse_program(Air& air, AirCfg& g, Next&& next, size_t cfg) {
+    const int32_t width = next(), nslots = next(), nconst = next(), nops = next(), nassert = next();
+    const std::string where = "AIR program (config " + std::to_string(cfg) + ")";
+    LSP_REQUIRE(width >= 1 && width <= (1 << 20), LSP_E_ARG, where + ": bad width");
+    LSP_REQUIRE(nslots >= 0 && nslots <= (int32_t)AIR_PROG_MAX_SLOTS, LSP_E_ARG, where + ": more than 16 slots");
+    LSP_REQUIRE(nconst >= 0 && nconst <= (1 << 16), LSP_E_ARG, where + ": more than 2^16 constants");
+    LSP_REQUIRE(nops >= 1 && nops <= (1 << 20), LSP_E_ARG, where + ": op count outside [1, 2^20]");
+    LSP_REQUIRE(nassert >= 1 && nassert <= nops, LSP_E_ARG, where + ": bad assert count");
+    g.nslots = (uint32_t)nslots;
+    g.nassert = (uint32_t)nassert;
+    air.dev.insert(air.dev.end(), {LSP_AIR_PROGRAM, width, nslots, nconst, nops, nassert});
+    for (int32_t i = 0; i < nconst; ++i) {
+        Fr c;
+        for (int k = 0; k < 8; ++k) c.v[k] = (uint32_t)next();
+        LSP_REQUIRE(fr_words_lt_mod(c), LSP_E_ARG, where + ": constant " + std::to_string(i) + " is not below r");
+        const Fr m = fr_from_canonical(c);
+        g.pconst.push_back(m);
+        // the device's form: the nine 29-bit limbs of c 2^261 mod r (fr29.hpp), canonical
+        const Fr x = fr_mul(m, fr_from_u64(32));
+        for (int l = 0; l < 9; ++l) {
+            const int bit = 29 * l, wd = bit >> 5, sh = bit & 31;
+            uint64_t v = x.v[wd];
+            if (wd + 1 < 8) v |= (uint64_t)x.v[wd + 1] << 32;
+            air.dev.push_back((int32_t)((uint32_t)(v >> sh) & (l < 8 ? 0x1fffffffu : 0xffffffffu)));
+        }
+    }
+    uint32_t written = 0, asserts = 0;  // slots written so far, a bit each
+    for (int32_t i = 0; i < nops; ++i) {
+        const std::string op = where + " op " + std::to_string(i);
+        const int32_t code = next(), dst = next(), a = next(), b = next();
+        auto operand = [&](int32_t x) {
+            const uint32_t kind = (uint32_t)x >> 24, v = (uint32_t)x & 0xffffffu;
+            switch (kind) {
+                case AIR_OPND_SLOT:
+                    LSP_REQUIRE(v < (uint32_t)nslots, LSP_E_ARG, op + ": slot past nslots");
+                    LSP_REQUIRE(written >> v & 1, LSP_E_ARG, op + ": slot read before it is written");
+                    break;
+                case AIR_OPND_LOCAL:
+                case AIR_OPND_NEXT:
+                    LSP_REQUIRE(v < (uint32_t)width, LSP_E_ARG, op + ": column outside the program's width");
+                    air.max_col = std::max(air.max_col, v);
+                    break;
+                case AIR_OPND_PUBLIC:
+                    LSP_REQUIRE(v < (1u << 16), LSP_E_ARG, op + ": public index 2^16 or more");
+                    air.max_pub = std::max<int64_t>(air.max_pub, v);
+                    break;
+                case AIR_OPND_CONST:
+                    LSP_REQUIRE(v < (uint32_t)nconst, LSP_E_ARG, op + ": constant past nconst");
+                    break;
+                case AIR_OPND_FIRST:
+                case AIR_OPND_LAST:
+                case AIR_OPND_TRANS:
+                    LSP_REQUIRE(v == 0, LSP_E_ARG, op + ": selector operand with a payload");
+                    break;
+                default: throw LspError(LSP_E_ARG, op + ": unknown operand kind");
+            }
+        };
+        if (code == AIR_OP_ASSERT_ZERO) {
+            LSP_REQUIRE(dst == 0 && b == 0, LSP_E_ARG, op + ": nonzero unused field");
+            operand(a);
+            ++asserts;
+        } else {
+            LSP_REQUIRE(code == AIR_OP_ADD || code == AIR_OP_SUB || code == AIR_OP_MUL, LSP_E_ARG,
+                        op + ": unknown opcode");
+            LSP_REQUIRE(dst >= 0 && dst < nslots, LSP_E_ARG, op + ": destination past nslots");
+            operand(a);
+            operand(b);
+            written |= 1u << dst;
+        }
+        g.pops.insert(g.pops.end(), {code, dst, a, b});
+    }
+    LSP_REQUIRE(asserts == (uint32_t)nassert, LSP_E_ARG, where + ": nassert is not the number of ASSERT_ZERO ops");
+    air.dev.insert(air.dev.end(), g.pops.begin(), g.pops.end());
+}
+
 Air Air::parse(const int32_t* d, size_t n) {
     Air air;
     LSP_REQUIRE(d && n >= 1, LSP_E_ARG, "empty AIR descriptor");
@@ -203,8 +283,10 @@ Air Air::parse(const int32_t* d, size_t n) {
     };
     const int32_t nc = next();
     LSP_REQUIRE(nc >= 1 && nc <= 4096, LSP_E_ARG, "bad config count in AIR descriptor");
+    air.dev.push_back(nc);
     for (int32_t c = 0; c < nc; ++c) {
         AirCfg g;
+        const size_t p0 = p;
         g.type = next();
         if (g.type == LSP_AIR_PERMUTATION) {
             const int32_t na = next(), nb = next();
@@ -228,13 +310,25 @@ Air Air::parse(const int32_t* d, size_t n) {
             for (int32_t t = 0; t < g.ntab; ++t) g.b_inv.push_back(col());
             for (int32_t t = 0; t < g.ntab; ++t) g.occ.push_back(col());
             g.check = col();
+        } else if (g.type == LSP_AIR_PROGRAM) {
+            parse_program(air, g, next, (size_t)c);  // (appends its device form to air.dev)
+            air.has_prog = true;
+            air.prog_slots = std::max(air.prog_slots, g.nslots);
         } else {
             throw LspError(LSP_E_ARG, "unknown AIR config type");
         }
+        if (g.type != LSP_AIR_PROGRAM) air.dev.insert(air.dev.end(), d + p0, d + p);
         air.cfgs.push_back(std::move(g));
     }
     LSP_REQUIRE(p == n, LSP_E_ARG, "trailing data in AIR descriptor");
     return air;
+}
+
+void Air::require_fits(size_t w, size_t npub) const {
+    LSP_REQUIRE(npub >= 2, LSP_E_ARG, "public values must hold [alpha, delta]");
+    LSP_REQUIRE(max_col < w, LSP_E_ARG, "AIR column id outside the trace width");
+    LSP_REQUIRE(max_pub < (int64_t)npub, LSP_E_ARG,
+                "AIR program reads public value " + std::to_string(max_pub) + " of " + std::to_string(npub));
 }
 
 // Symbolic degree_multiple rules of p3-uni-stark: main variables 1,
@@ -246,10 +340,60 @@ static int horner_deg(size_t n, int pd) {
     return d;
 }
 
+// a program's asserts by the same rule, tracked slot by slot
+static void program_degrees(const AirCfg& g, int pd, std::vector<int>& out) {
+    int slot[AIR_PROG_MAX_SLOTS] = {0};
+    auto deg = [&](int32_t x) {
+        switch ((uint32_t)x >> 24) {
+            case AIR_OPND_SLOT: return slot[(uint32_t)x & 0xffffffu];
+            case AIR_OPND_LOCAL:
+            case AIR_OPND_NEXT:
+            case AIR_OPND_FIRST:
+            case AIR_OPND_LAST: return 1;
+            case AIR_OPND_PUBLIC: return pd;
+            default: return 0;  // constants, IsTransition
+        }
+    };
+    for (size_t i = 0; i < g.pops.size(); i += 4) {
+        const int32_t* o = g.pops.data() + i;
+        if (o[0] == AIR_OP_ASSERT_ZERO) {
+            out.push_back(deg(o[2]));
+            continue;
+        }
+        const int a = deg(o[2]), b = deg(o[3]);
+        // (saturating: 2^20 squarings would overflow, and any such degree is far past every blowup)
+        slot[o[1]] = o[0] == AIR_OP_MUL ? std::min(a + b, 1 << 30) : std::max(a, b);
+    }
+}
+
+std::vector<int> Air::degrees(int pd) const {
+    std::vector<int> out;
+    for (const auto& g : cfgs) {
+        if (g.type == LSP_AIR_PROGRAM) {
+            program_degrees(g, pd, out);
+        } else if (g.type == LSP_AIR_PERMUTATION) {
+            const int a = std::max(horner_deg(g.a.size(), pd), pd), b = std::max(horner_deg(g.b.size(), pd), pd);
+            out.insert(out.end(), {b + 1, 1 + std::max(1, a + 1), std::max(1, a + 2), 2});
+        } else {
+            const int a = std::max(horner_deg(g.a.size(), pd), pd);
+            const int bdeg = std::max(horner_deg((size_t)g.nbc, pd), pd);
+            out.push_back(a + 1);
+            for (int32_t t = 0; t < g.ntab; ++t) out.push_back(bdeg + 1);
+            out.insert(out.end(), {1 + 3, 3, 2});  // the LogUp sums are products of three columns
+        }
+    }
+    return out;
+}
+
 std::pair<int, int> Air::stats(int pd) const {
     int maxd = 0, k = 0;
     for (const auto& g : cfgs) {
-        if (g.type == LSP_AIR_PERMUTATION) {
+        if (g.type == LSP_AIR_PROGRAM) {
+            std::vector<int> dg;
+            program_degrees(g, pd, dg);
+            for (int x : dg) maxd = std::max(maxd, x);
+            k += (int)g.nassert;
+        } else if (g.type == LSP_AIR_PERMUTATION) {
             const int a = std::max(horner_deg(g.a.size(), pd), pd), b = std::max(horner_deg(g.b.size(), pd), pd);
             maxd = std::max({maxd, b + 1, 1 + std::max(1, a + 1), std::max(1, a + 2), 2});
             k += 4;
@@ -273,23 +417,27 @@ uint32_t Air::log_quotient_degree(int pd) const {
     return lg;
 }
 
-void Air::eval_fold(const Fr* loc, const Fr* nxt, const Fr& ap, const Fr& dl, const Fr& first, const Fr& last,
-                    const Fr& trans, const Fr& al, Fr& acc) const {
-    eval(loc, nxt, ap, dl, first, last, trans, [&](const Fr& x) { acc = fr_add(fr_mul(acc, al), x); });
+void Air::eval_fold(const Fr* loc, const Fr* nxt, const Fr* pub, const Fr& first, const Fr& last, const Fr& trans,
+                    const Fr& al, Fr& acc) const {
+    eval(loc, nxt, pub, first, last, trans, [&](const Fr& x) { acc = fr_add(fr_mul(acc, al), x); });
 }
 
 Air::ConsInfo Air::constraint_info(uint32_t j) const {
     uint32_t k = 0;
     for (size_t c = 0; c < cfgs.size(); ++c) {
         const AirCfg& g = cfgs[c];
-        const uint32_t n = g.type == LSP_AIR_PERMUTATION ? 4 : 4 + (uint32_t)g.ntab;
+        const uint32_t n = g.type == LSP_AIR_PROGRAM       ? g.nassert
+                           : g.type == LSP_AIR_PERMUTATION ? 4
+                                                           : 4 + (uint32_t)g.ntab;
         if (j >= k + n) {
             k += n;
             continue;
         }
         const uint32_t i = j - k;
         ConsInfo o{(uint32_t)c, g.type, 0, -1};
-        if (g.type == LSP_AIR_PERMUTATION) {
+        if (g.type == LSP_AIR_PROGRAM) {
+            o.kind = LSP_CONSTRAINT_PROGRAM;
+        } else if (g.type == LSP_AIR_PERMUTATION) {
             static const int32_t kinds[4] = {LSP_CONSTRAINT_B_INVERSE, LSP_CONSTRAINT_FIRST_ROW,
                                              LSP_CONSTRAINT_TRANSITION, LSP_CONSTRAINT_LAST_ROW};
             o.kind = kinds[i];

@@ -214,29 +214,55 @@ struct Challenger {
     }
 };
 
+// LSP_AIR_PROGRAM operands and opcodes (include/lsp.h)
+enum : uint32_t {
+    AIR_OPND_SLOT = 0, AIR_OPND_LOCAL = 1, AIR_OPND_NEXT = 2, AIR_OPND_PUBLIC = 3, AIR_OPND_CONST = 4,
+    AIR_OPND_FIRST = 5, AIR_OPND_LAST = 6, AIR_OPND_TRANS = 7
+};
+enum : int32_t { AIR_OP_ADD = 1, AIR_OP_SUB = 2, AIR_OP_MUL = 3, AIR_OP_ASSERT_ZERO = 4 };
+constexpr uint32_t AIR_PROG_MAX_SLOTS = 16;
+
 struct AirCfg {
-    int type;  // 1 perm, 2 lookup
+    int type;  // 1 perm, 2 lookup, 3 program
     std::vector<int32_t> a, b;             // perm: a, b ; lookup: a, flattened b tables
     int32_t binv = 0, check = 0;           // perm
     int32_t ntab = 0, nbc = 0, a_filter = 0, a_inv = 0;
     std::vector<int32_t> b_filter, b_inv, occ;
+    // program: its constants (Montgomery form) and ops as [opcode, dst, a, b]
+    uint32_t nslots = 0, nassert = 0;
+    std::vector<Fr> pconst;
+    std::vector<int32_t> pops;
 };
 struct Air {
     std::vector<AirCfg> cfgs;
     std::vector<int32_t> raw;
     uint32_t max_col = 0;
+    // programs: whether the descriptor holds one, the largest register file
+    // among them, the highest public value any reads (-1: none), and the
+    // descriptor as the kernels read it (k_air_prog.hpp: each constant as the
+    // nine 29-bit limbs of its 2^261 form)
+    bool has_prog = false;
+    uint32_t prog_slots = 0;
+    int64_t max_pub = -1;
+    std::vector<int32_t> dev;
     static Air parse(const int32_t* d, size_t n);
+    // what only a call knows: every column id < w, every public index < npub
+    void require_fits(size_t w, size_t npub) const;
+    // every constraint's degree under the U6 public-degree rule, in eval's order
+    std::vector<int> degrees(int public_degree) const;
     // (max constraint degree, constraint count) under the U6 public-degree rule
     std::pair<int, int> stats(int public_degree) const;
     uint32_t log_quotient_degree(int public_degree) const;
     // LineaAIR::eval on concrete values: push(x) gets every constraint's value
-    // (already multiplied by its selector) in eval's order
+    // (already multiplied by its selector) in eval's order.  pub = [alpha,
+    // delta, ...]: programs read any of them (require_fits has checked their
+    // indices) and take the selectors as operands like any other
     template <class Push>
-    void eval(const Fr* loc, const Fr* nxt, const Fr& ap, const Fr& dl, const Fr& first, const Fr& last,
-              const Fr& trans, Push&& push) const;
+    void eval(const Fr* loc, const Fr* nxt, const Fr* pub, const Fr& first, const Fr& last, const Fr& trans,
+              Push&& push) const;
     // concrete evaluation folded into acc (verifier / tests)
-    void eval_fold(const Fr* loc, const Fr* nxt, const Fr& ap, const Fr& dl, const Fr& first, const Fr& last,
-                   const Fr& trans, const Fr& alpha, Fr& acc) const;
+    void eval_fold(const Fr* loc, const Fr* nxt, const Fr* pub, const Fr& first, const Fr& last, const Fr& trans,
+                   const Fr& alpha, Fr& acc) const;
     // what constraint j of eval's order is (lsp_air_constraint_info); LSP_E_ARG when j is past the end
     struct ConsInfo {
         uint32_t config;
@@ -253,11 +279,36 @@ inline Fr air_horner(const Fr* row, const int32_t* ids, size_t n, const Fr& a) {
 }
 
 template <class Push>
-void Air::eval(const Fr* loc, const Fr* nxt, const Fr& ap, const Fr& dl, const Fr& first, const Fr& last,
-               const Fr& trans, Push&& push) const {
+void Air::eval(const Fr* loc, const Fr* nxt, const Fr* pub, const Fr& first, const Fr& last, const Fr& trans,
+               Push&& push) const {
     const Fr one = fr_one();
+    const Fr &ap = pub[0], &dl = pub[1];
     for (const auto& g : cfgs) {
-        if (g.type == LSP_AIR_PERMUTATION) {
+        if (g.type == LSP_AIR_PROGRAM) {
+            Fr slot[AIR_PROG_MAX_SLOTS];
+            auto opnd = [&](int32_t x) -> Fr {
+                const uint32_t k = (uint32_t)x >> 24, v = (uint32_t)x & 0xffffffu;
+                switch (k) {
+                    case AIR_OPND_SLOT: return slot[v];
+                    case AIR_OPND_LOCAL: return loc[v];
+                    case AIR_OPND_NEXT: return nxt[v];
+                    case AIR_OPND_PUBLIC: return pub[v];
+                    case AIR_OPND_CONST: return g.pconst[v];
+                    case AIR_OPND_FIRST: return first;
+                    case AIR_OPND_LAST: return last;
+                    default: return trans;
+                }
+            };
+            for (size_t i = 0; i < g.pops.size(); i += 4) {
+                const int32_t* o = g.pops.data() + i;
+                if (o[0] == AIR_OP_ASSERT_ZERO) {
+                    push(opnd(o[2]));
+                    continue;
+                }
+                const Fr x = opnd(o[2]), y = opnd(o[3]);
+                slot[o[1]] = o[0] == AIR_OP_ADD ? fr_add(x, y) : o[0] == AIR_OP_SUB ? fr_sub(x, y) : fr_mul(x, y);
+            }
+        } else if (g.type == LSP_AIR_PERMUTATION) {
             const Fr a_l = fr_add(air_horner(loc, g.a.data(), g.a.size(), ap), dl);
             const Fr b_l = fr_add(air_horner(loc, g.b.data(), g.b.size(), ap), dl);
             push(fr_sub(fr_mul(b_l, loc[g.binv]), one));

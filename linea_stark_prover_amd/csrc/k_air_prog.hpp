@@ -1,0 +1,125 @@
+// The interpreter of LSP_AIR_PROGRAM configs (include/lsp.h), shared by the
+// program-capable instantiations of k_quotient.hip and k_check.hip: a
+// straight-line program of ADD / SUB / MUL over field registers ("slots") whose
+// ASSERT_ZERO ops hand out the constraint values in order.
+//
+// Device form of a config (Air::parse writes it, Air::dev): the descriptor's
+// words with every constant replaced by the nine 29-bit limbs of its 2^261
+// form, canonical -- so a constant operand is nine scalar loads and no
+// conversion:
+//   3, width, nslots, nconst, nops, nassert, const[nconst][9], op[nops][4]
+//
+// Register file: LDS, not an indexed local array (the compiler sends a
+// runtime-indexed array to scratch).  Limb-planar: slot s, limb l of thread t
+// at regs[(s * 9 + l) * blockDim.x + t], so a wave's 64 lanes read 64
+// adjacent words (no bank conflict), 36 bytes x blockDim.x per slot, sized by
+// the launch from the largest nslots of the descriptor (dynamic shared
+// memory).  A thread touches only its own column: no barrier.
+//
+// Control flow is wave-uniform: opcode, operand kinds and payloads come from
+// the descriptor, which every lane reads at the same index, so every lane
+// executes every op (k_check's ballots rely on it) and the descriptor reads
+// are scalar loads.
+//
+// Bounds of the arithmetic (Q29 of the two kernels, fr29.hpp).  An operand is
+//   a loaded cell or public value   f29_from_fr: normalised, < 2 r
+//   a constant                      canonical: normalised, < r
+//   a selector                      the quotient's are products (< 8.92 r) or
+//                                   x - w^-1 (< 2 r); the check's are 0 or 1
+//   a slot                          the result of an earlier op: add / sub
+//                                   leave normalised and < 2 r, mul normalised
+//                                   and < 8.92 r
+// so every operand is normalised and < 8.92 r.  add takes two of them (sum
+// < 17.84 r, limbs < 2^30; f29_reduce_qt takes < 64 r, limbs < 2.41 2^30),
+// sub a subtrahend < 16 r (a + 16 r - b < 24.92 r, limbs < 1.5 2^30), mul
+// inputs < 20 r.  The op set is closed: whatever a program computes, no op
+// sees a value outside what it accepts (tests/test_air_program.py models it).
+#pragma once
+#include "fr29.hpp"
+#include "k_common.hpp"
+
+namespace lsp {
+
+// what one thread evaluates a program on
+struct ProgEnv {
+    const Fr* loc;
+    const Fr* nxt;
+    uint32_t w;          // row width (the host has checked every column against it)
+    const Fr* pub;       // device table of the public values
+    uint32_t npub;
+    F29 first, last, trans;  // the selector operands
+    uint32_t* regs;      // the block's register file
+    uint32_t lds_slots;  // slots it was sized for
+};
+
+__device__ __forceinline__ F29 prog_slot_ld(const ProgEnv& e, uint32_t s) {
+    F29 v = f29_zero();
+    if (!LSP_BOUNDS(s < e.lds_slots)) return v;
+    const uint32_t* r = e.regs + (size_t)s * 9 * blockDim.x + threadIdx.x;
+#pragma unroll
+    for (int l = 0; l < 9; ++l) v.l[l] = r[(size_t)l * blockDim.x];
+    return v;
+}
+
+__device__ __forceinline__ void prog_slot_st(const ProgEnv& e, uint32_t s, const F29& v) {
+    if (!LSP_BOUNDS(s < e.lds_slots)) return;
+    uint32_t* r = e.regs + (size_t)s * 9 * blockDim.x + threadIdx.x;
+#pragma unroll
+    for (int l = 0; l < 9; ++l) r[(size_t)l * blockDim.x] = v.l[l];
+}
+
+__device__ __forceinline__ F29 prog_operand(const ProgEnv& e, const int32_t* __restrict__ cst, uint32_t nconst,
+                                            int32_t x) {
+    const uint32_t kind = (uint32_t)x >> 24, v = (uint32_t)x & 0xffffffu;
+    switch (kind) {
+        case 0: return prog_slot_ld(e, v);
+        case 1: return LSP_BOUNDS(v < e.w) ? f29_from_fr(e.loc[v]) : f29_zero();
+        case 2: return LSP_BOUNDS(v < e.w) ? f29_from_fr(e.nxt[v]) : f29_zero();
+        case 3: return LSP_BOUNDS(v < e.npub) ? f29_from_fr(e.pub[v]) : f29_zero();
+        case 4: {
+            F29 c = f29_zero();
+            if (LSP_BOUNDS(v < nconst)) {
+#pragma unroll
+                for (int l = 0; l < 9; ++l) c.l[l] = (uint32_t)cst[(size_t)v * 9 + l];
+            }
+            return c;
+        }
+        case 5: return e.first;
+        case 6: return e.last;
+        default: return e.trans;
+    }
+}
+
+// Run the program config whose words follow its type word at d[p]; returns the
+// index past the config.  on_assert(v) gets each ASSERT_ZERO's value as its
+// operand stands (normalised, < 8.92 r), in order.
+template <class Q, class Assert>
+__device__ __forceinline__ int32_t air_prog_run(const Q& F, const ProgEnv& e, const int32_t* __restrict__ d, int32_t p,
+                                                Assert&& on_assert) {
+    const uint32_t nconst = (uint32_t)d[p + 2], nops = (uint32_t)d[p + 3];
+    const int32_t* cst = d + p + 5;
+    const int32_t* op = cst + (size_t)nconst * 9;
+    for (uint32_t i = 0; i < nops; ++i, op += 4) {
+        const int32_t code = op[0];
+        const F29 x = prog_operand(e, cst, nconst, op[2]);
+        if (code == 4) {
+            on_assert(x);
+            continue;
+        }
+        const F29 y = prog_operand(e, cst, nconst, op[3]);
+        prog_slot_st(e, (uint32_t)op[1], code == 3 ? F.mul(x, y) : code == 1 ? F.add(x, y) : F.sub(x, y));
+    }
+    return p + 5 + (int32_t)(nconst * 9 + nops * 4);
+}
+
+// bytes of dynamic shared memory for a register file of `slots` slots
+inline size_t air_prog_lds_bytes(uint32_t slots, uint32_t block) { return (size_t)slots * 9 * block * sizeof(uint32_t); }
+// Block size of a program-capable launch.  Up to 8 slots: 256 threads (at 8
+// slots 73.7 KB of slots + the 3 KB reduction table per block, two blocks =
+// 8 waves per CU, 2 per SIMD, inside the CU's 160 KB).  9 to 16 slots take 324
+// to 576 bytes per thread, so at most 7 down to 4 waves fit a CU whatever the
+// block size: 128 threads keep the granularity fine (16 slots: two blocks of
+// 73.7 KB, one wave per SIMD).
+inline uint32_t air_prog_block(uint32_t slots) { return slots <= 8 ? 256u : 128u; }
+
+}  // namespace lsp

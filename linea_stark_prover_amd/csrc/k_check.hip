@@ -26,6 +26,7 @@
 // run in.  k_check_rows re-evaluates a short list of rows and writes every
 // constraint's canonical value (the detail records of the report).
 #include "fr29.hpp"
+#include "k_air_prog.hpp"
 #include "k_common.hpp"
 #include "kernels.hpp"
 
@@ -76,8 +77,13 @@ __device__ __forceinline__ bool f29_is_zero_mod_r(const F29& v) {
 }
 
 // LineaAIR::eval on one row pair: push(value, selector) per constraint in
-// eval's order, value normalised and < 2 r, not multiplied by the selector
-template <class Push>
+// eval's order, value normalised and < 2 r, not multiplied by the selector.
+// PROG: also run LSP_AIR_PROGRAM configs (k_air_prog.hpp; an instantiation of
+// its own, as in k_quotient.hip).  A program takes the 0/1 selectors as data
+// wherever it names them, so its asserts are pushed under `always`; an asserted
+// operand may be a raw product (< 8.92 r), a selector or a constant, and goes
+// through one reduction first (normalised, < 2 r: what the zero test needs).
+template <bool PROG, class Push>
 __device__ __forceinline__ void check_walk(const Q29& F, const CheckArgs& a, const Fr* __restrict__ loc,
                                            const Fr* __restrict__ nxt, bool first, bool last, Push&& push) {
     const bool trans = !last, always = true;
@@ -103,7 +109,7 @@ __device__ __forceinline__ void check_walk(const Q29& F, const CheckArgs& a, con
             const F29 a_n = F.add(horner(F, nxt, aid, na, ap, a.w), dl);
             push(F.sub(ld29(nxt, chk, a.w), F.mul(F.mul(lchk, a_n), ld29(nxt, binv, a.w))), trans);
             push(F.sub(lchk, one), last);
-        } else {  // AirLookupConfig: air/src/lib.rs:57-114
+        } else if (!PROG || type == 2) {  // AirLookupConfig: air/src/lib.rs:57-114
             const int32_t na = d[p++];
             const int32_t* aid = d + p;
             p += na;
@@ -135,10 +141,17 @@ __device__ __forceinline__ void check_walk(const Q29& F, const CheckArgs& a, con
             push(F.sub(lchk, lc), first);
             push(F.sub(F.sub(ld29(nxt, chk, a.w), lchk), nc), trans);
             push(lchk, last);
+        } else if constexpr (PROG) {
+            extern __shared__ uint32_t prog_regs[];
+            const F29 zero = f29_zero();
+            const ProgEnv e{loc,         nxt, a.w, a.pub, a.npub, first ? one : zero, last ? one : zero,
+                            trans ? one : zero, prog_regs, a.prog_slots};
+            p = air_prog_run(F, e, d, p, [&](const F29& v) { push(f29_reduce_qt(v, F.qt), always); });
         }
     }
 }
 
+template <bool PROG>
 __global__ __launch_bounds__(256) void k_check(CheckArgs a) {
     __shared__ uint4 qt[3 * F29_QTAB_N];  // f29_reduce_qt's table
     f29_qtab_init(qt);
@@ -159,7 +172,7 @@ __global__ __launch_bounds__(256) void k_check(CheckArgs a) {
     unsigned long long* first_row = reinterpret_cast<unsigned long long*>(a.first_row);
     uint32_t j = 0;
     bool any = false;
-    check_walk(F, a, loc, nxt, i == 0, i + 1 == a.h, [&](const F29& v, bool sel) {
+    check_walk<PROG>(F, a, loc, nxt, i == 0, i + 1 == a.h, [&](const F29& v, bool sel) {
         const bool bad = live && sel && !f29_is_zero_mod_r(v);
         const unsigned long long m = __ballot(bad);
         any |= bad;
@@ -173,6 +186,7 @@ __global__ __launch_bounds__(256) void k_check(CheckArgs a) {
     if (lane == 0 && LSP_BOUNDS(row0 / 64 < (a.h + 63) / 64)) a.row_mask[row0 / 64] = m;
 }
 
+template <bool PROG>
 __global__ __launch_bounds__(64) void k_check_rows(CheckArgs a) {
     __shared__ uint4 qt[3 * F29_QTAB_N];
     f29_qtab_init(qt);
@@ -187,7 +201,7 @@ __global__ __launch_bounds__(64) void k_check_rows(CheckArgs a) {
     }
     const uint64_t in = i + 1 == a.h ? 0 : i + 1;
     uint32_t j = 0;
-    check_walk(F, a, a.trace + i * a.w, a.trace + in * a.w, i == 0, i + 1 == a.h, [&](const F29& v, bool sel) {
+    check_walk<PROG>(F, a, a.trace + i * a.w, a.trace + in * a.w, i == 0, i + 1 == a.h, [&](const F29& v, bool sel) {
         const Fr x = f29_to_fr_qt(v, qt);  // canonical, ark form
         if (live && LSP_BOUNDS(j < a.ncons)) a.vals[t * a.ncons + j] = sel ? x : fr_zero();
         ++j;
@@ -197,13 +211,31 @@ __global__ __launch_bounds__(64) void k_check_rows(CheckArgs a) {
 
 hipError_t launch_check(const CheckArgs& a, hipStream_t st) {
     if (!a.h || !a.row_mask || !a.count || !a.first_row) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_check, dim3(nblocks(a.h, 256)), dim3(256), 0, st, a);
+    if (a.prog) {
+        if (!a.pub || a.npub < 2 || a.prog_slots > 16) return hipErrorInvalidValue;
+        const uint32_t bs = air_prog_block(a.prog_slots);
+        const size_t lds = air_prog_lds_bytes(a.prog_slots, bs);
+        if (lds > 48 * 1024) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_check<true>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(k_check<true>, dim3(nblocks(a.h, bs)), dim3(bs), lds, st, a);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(k_check<false>, dim3(nblocks(a.h, 256)), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
 hipError_t launch_check_rows(const CheckArgs& a, hipStream_t st) {
     if (!a.h || !a.nrows || !a.rows || !a.vals) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_check_rows, dim3(nblocks(a.nrows, 64)), dim3(64), 0, st, a);
+    if (a.prog) {  // 64 threads: 16 slots are 36 KB
+        if (!a.pub || a.npub < 2 || a.prog_slots > 16) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_check_rows<true>, dim3(nblocks(a.nrows, 64)), dim3(64),
+                           air_prog_lds_bytes(a.prog_slots, 64), st, a);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(k_check_rows<false>, dim3(nblocks(a.nrows, 64)), dim3(64), 0, st, a);
     return hipGetLastError();
 }
 

@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 #include "fr29.hpp"
+#include "k_air_prog.hpp"
 #include "k_common.hpp"
 #include "kernels.hpp"
 
@@ -64,8 +65,11 @@ __device__ __forceinline__ void st_cons(const QuotientArgs& a, uint32_t j, size_
     for (int l = 0; l < 9; ++l) c[(size_t)l * n] = v.l[l];
 }
 
-// EARLY: write the constraint values (QuotientArgs::cons) instead of folding them
-template <bool EARLY>
+// EARLY: write the constraint values (QuotientArgs::cons) instead of folding them.
+// PROG: also run LSP_AIR_PROGRAM configs (k_air_prog.hpp) -- an instantiation
+// of its own, launched only for a descriptor that holds one, so that the walker
+// of the built-in configs keeps its code, registers and LDS.
+template <bool EARLY, bool PROG>
 __global__ __launch_bounds__(256) void k_quotient(QuotientArgs a) {
     __shared__ uint4 qt[3 * F29_QTAB_N];  // f29_reduce_qt's table
     f29_qtab_init(qt);
@@ -133,7 +137,7 @@ __global__ __launch_bounds__(256) void k_quotient(QuotientArgs a) {
             const F29 a_n = F.add(horner(F, nxt, aid, na, ap, a.w), dl);
             PUSH(F.mul(trans, F.sub(ld29(nxt, chk, a.w), F.mul(F.mul(lchk, a_n), ld29(nxt, binv, a.w)))));
             PUSH(F.mul(last, F.sub(lchk, one)));
-        } else {  // AirLookupConfig: air/src/lib.rs:57-114
+        } else if (!PROG || type == 2) {  // AirLookupConfig: air/src/lib.rs:57-114
             const int32_t na = d[p++];
             const int32_t* aid = d + p;
             p += na;
@@ -165,6 +169,10 @@ __global__ __launch_bounds__(256) void k_quotient(QuotientArgs a) {
             PUSH(F.mul(first, F.sub(lchk, lc)));
             PUSH(F.mul(trans, F.sub(F.sub(ld29(nxt, chk, a.w), lchk), nc)));
             PUSH(F.mul(last, lchk));
+        } else if constexpr (PROG) {  // LSP_AIR_PROGRAM: the selectors are operands, an assert's value is pushed as it stands
+            extern __shared__ uint32_t prog_regs[];
+            const ProgEnv e{loc, nxt, a.w, a.pub, a.npub, first, last, trans, prog_regs, a.prog_slots};
+            p = air_prog_run(F, e, d, p, [&](const F29& v) { PUSH(v); });
         }
     }
 #undef PUSH
@@ -219,13 +227,34 @@ static QuotientArgs with_order(const QuotientArgs& a) {
     return b;
 }
 
+// The program-capable walker: its register file is dynamic shared memory sized
+// by the descriptor's largest nslots (k_air_prog.hpp); more than 48 KB of it
+// (6 slots and up at 256 threads) is asked for by attribute first.
+template <bool EARLY>
+static hipError_t launch_quotient_prog_t(const QuotientArgs& b, size_t n, hipStream_t st) {
+    if (!b.pub || b.npub < 2 || b.prog_slots > 16) return hipErrorInvalidValue;
+    const uint32_t bs = air_prog_block(b.prog_slots);
+    const size_t lds = air_prog_lds_bytes(b.prog_slots, bs);
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_quotient<EARLY, true>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((k_quotient<EARLY, true>), dim3(nblocks(n, bs)), dim3(bs), lds, st, b);
+    return hipGetLastError();
+}
+static hipError_t launch_quotient_prog(const QuotientArgs& b, size_t n, hipStream_t st) {
+    return b.cons ? launch_quotient_prog_t<true>(b, n, st) : launch_quotient_prog_t<false>(b, n, st);
+}
+
 hipError_t launch_quotient(const QuotientArgs& a, hipStream_t st) {
     const size_t n = a.n ? a.n : (1ull << a.logQ);
     const QuotientArgs b = with_order(a);
+    if (a.prog) return launch_quotient_prog(b, n, st);
     if (a.cons)
-        hipLaunchKernelGGL(k_quotient<true>, dim3(nblocks(n, 256)), dim3(256), 0, st, b);
+        hipLaunchKernelGGL((k_quotient<true, false>), dim3(nblocks(n, 256)), dim3(256), 0, st, b);
     else
-        hipLaunchKernelGGL(k_quotient<false>, dim3(nblocks(n, 256)), dim3(256), 0, st, b);
+        hipLaunchKernelGGL((k_quotient<false, false>), dim3(nblocks(n, 256)), dim3(256), 0, st, b);
     return hipGetLastError();
 }
 

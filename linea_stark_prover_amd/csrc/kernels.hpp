@@ -221,6 +221,14 @@ struct QuotientArgs {
     // launch_quotient_fold then folds them with `alpha` and 1/Z_H into `out`
     uint32_t* cons = nullptr;
     uint32_t ncons = 0;
+    // LSP_AIR_PROGRAM configs (k_air_prog.hpp).  prog != 0: the descriptor
+    // holds one (constants as nine 29-bit limbs each), so launch_quotient runs
+    // the program-capable walker with a register file of prog_slots slots per
+    // thread in LDS; `pub` is the device table of all npub public values.
+    // prog = 0: the built-in walker, which reads none of these.
+    const Fr* pub = nullptr;
+    uint32_t npub = 0;
+    uint32_t prog = 0, prog_slots = 0;
 };
 // den[m] = (x_i - 1)(x_i - w_h^-1), x_i = GEN * w_Q^i, i = i0 + (m << log_step), m < n
 hipError_t launch_selector_denoms(const Fr* tabQ, uint32_t L1, Fr gen, Fr wh_inv, size_t n, Fr* den,
@@ -251,6 +259,10 @@ struct CheckArgs {
     const uint64_t* rows = nullptr;
     uint32_t nrows = 0;
     Fr* vals = nullptr;
+    // LSP_AIR_PROGRAM configs, as in QuotientArgs
+    const Fr* pub = nullptr;
+    uint32_t npub = 0;
+    uint32_t prog = 0, prog_slots = 0;
 };
 hipError_t launch_check(const CheckArgs& a, hipStream_t st);
 hipError_t launch_check_rows(const CheckArgs& a, hipStream_t st);

@@ -185,8 +185,7 @@ struct Shard {
 };
 
 Shard shard_geometry(const lsp_ctx* ctx, const Comm& comm, size_t h, size_t w, const Air& air, size_t npub) {
-    LSP_REQUIRE(npub >= 2, LSP_E_ARG, "public values must hold [alpha, delta]");
-    LSP_REQUIRE(air.max_col < w, LSP_E_ARG, "AIR column id outside the trace width");
+    air.require_fits(w, npub);
     Shard s;
     s.h = h;
     s.w = w;
@@ -238,6 +237,7 @@ struct Prover {
     const Fr* const d_trace;
     const Air& air;
     const Fr* const pub;
+    const size_t npub;
     const Shard s;
     const hipStream_t st;
     const Fr GEN = host_generator(), one = fr_one();
@@ -279,9 +279,9 @@ struct Prover {
     // LSP_TIME_TOPS
     host_clock::time_point t_entry, t_lde_issued, q0, q1, q2, q3;
 
-    Prover(lsp_ctx* c, Comm& cm, const Fr* trace, const Air& a, const Fr* pv, const Shard& geo,
+    Prover(lsp_ctx* c, Comm& cm, const Fr* trace, const Air& a, const Fr* pv, size_t npv, const Shard& geo,
            host_clock::time_point entry)
-        : ctx(c), comm(cm), d_trace(trace), air(a), pub(pv), s(geo), st(c->stream),
+        : ctx(c), comm(cm), d_trace(trace), air(a), pub(pv), npub(npv), s(geo), st(c->stream),
           wh(host_two_adic_generator(geo.log_h)), wh_inv(host_inv_cached(wh)), T(c), proof(new lsp_proof()),
           t_entry(entry) {
         ctx->spans.clear();
@@ -387,7 +387,7 @@ struct Prover {
             }
         }
         if (s.row0 >= Q) return;
-        quotient_domain(ctx, s.log_h, s.log_q, host_bitrev(g, s.logGq), s.logGq, Sq, air, pub[0], pub[1], qa);
+        quotient_domain(ctx, s.log_h, s.log_q, host_bitrev(g, s.logGq), s.logGq, Sq, air, pub, npub, qa);
         qa.lde = lde;
         qa.w = (uint32_t)w;
         qa.out = qloc;
@@ -989,7 +989,7 @@ lsp_proof* prove_shard(lsp_ctx* ctx, Comm& comm, const Fr* d_trace, size_t h, si
     const DeferTopUploads defer(ctx);
     comm.begin_log(ctx);
     const Shard geo = shard_geometry(ctx, comm, h, w, air, npub);
-    Prover P(ctx, comm, d_trace, air, pub, geo, t_entry);
+    Prover P(ctx, comm, d_trace, air, pub, npub, geo, t_entry);
 
     P.commit_trace();
     // U7: the instance, then the quotient challenge (TranscriptCfg switches)

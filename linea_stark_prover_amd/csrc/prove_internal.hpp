@@ -33,7 +33,7 @@ void subcoset_lde(lsp_ctx* ctx, const Fr* coef, ColMap map, size_t h, size_t w, 
 // inv_zh, inv_den, i0, log_step, n).  Owns the context's "qsel_*" cache of
 // inverted selector denominators.
 void quotient_domain(lsp_ctx* ctx, uint32_t log_h, uint32_t log_q, uint64_t i0, uint32_t log_step, size_t n,
-                     const Air& air, const Fr& pub_alpha, const Fr& pub_delta, QuotientArgs& qa);
+                     const Air& air, const Fr* pub, size_t npub, QuotientArgs& qa);
 // out[i] = 1 / (z - shift w_N^bitrev(row0 + i)), i < n.  inv_total (optional):
 // 1 / (the product of the n denominators) where the caller knows it in closed form
 void open_denominators(lsp_ctx* ctx, const Fr& z, const Fr& shift, uint32_t logN, uint64_t row0, size_t n, Fr* out,

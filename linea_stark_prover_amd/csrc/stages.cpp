@@ -16,7 +16,7 @@ namespace lsp {
 
 // ------------------------------------------------------------ quotient
 void quotient_domain(lsp_ctx* ctx, uint32_t log_h, uint32_t log_q, uint64_t i0, uint32_t log_step, size_t n,
-                     const Air& air, const Fr& pub_alpha, const Fr& pub_delta, QuotientArgs& qa) {
+                     const Air& air, const Fr* pub, size_t npub, QuotientArgs& qa) {
     const uint32_t logQ = log_h + log_q;
     const size_t h = (size_t)1 << log_h, q = (size_t)1 << log_q;
     if (n == 0) n = ((size_t)1 << logQ) >> log_step;
@@ -55,14 +55,23 @@ void quotient_domain(lsp_ctx* ctx, uint32_t log_h, uint32_t log_q, uint64_t i0, 
     }
     Fr* dzh = ctx->fbuf("q_zh", 2 * q);
     ctx->h2d_async("q_zh_h", dzh, zh.data(), 2 * q * sizeof(Fr));
-    int32_t* dair = (int32_t*)ctx->buf("air", air.raw.size() * sizeof(int32_t));
-    ctx->h2d_async("air_h", dair, air.raw.data(), air.raw.size() * sizeof(int32_t));
+    // (air.dev is air.raw unless the descriptor holds a program)
+    int32_t* dair = (int32_t*)ctx->buf("air", air.dev.size() * sizeof(int32_t));
+    ctx->h2d_async("air_h", dair, air.dev.data(), air.dev.size() * sizeof(int32_t));
     qa.logQ = logQ;
     qa.log_q = log_q;
     qa.air = dair;
-    qa.air_len = (uint32_t)air.raw.size();
-    qa.pub_alpha = pub_alpha;
-    qa.pub_delta = pub_delta;
+    qa.air_len = (uint32_t)air.dev.size();
+    qa.pub_alpha = pub[0];
+    qa.pub_delta = pub[1];
+    if (air.has_prog) {  // programs read the public values from a table
+        Fr* dpub = ctx->fbuf("q_pub", npub);
+        ctx->h2d_async("q_pub_h", dpub, pub, npub * sizeof(Fr));
+        qa.pub = dpub;
+        qa.npub = (uint32_t)npub;
+        qa.prog = 1;
+        qa.prog_slots = air.prog_slots;
+    }
     qa.gen = GEN;
     qa.wh_inv = wh_inv;
     qa.tabQ = tabQ;

@@ -62,7 +62,7 @@ int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, 
     r.off = 8;
     const uint32_t log_h = r.u32(), log_q = r.u32(), w = r.u32(), nq = r.u32(), nr = r.u32(), nf = r.u32();
     if (r.bad || log_q != air.log_quotient_degree(ctx->public_degree) || nq != ctx->num_queries || log_h > 40 ||
-        log_h < 1 || w <= air.max_col || w > (1u << 20))
+        log_h < 1 || w <= air.max_col || w > (1u << 20) || air.max_pub >= (int64_t)npub)
         return 3;
     const uint32_t lb = ctx->log_blowup, logN = log_h + lb;
     if (nr != logN - lb - ctx->log_final_poly_len || nf != (1u << ctx->log_final_poly_len)) return 4;
@@ -168,7 +168,7 @@ int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, 
     const Fr last = fr_mul(zh, fr_inv(fr_sub(zeta, wh_inv)));
     const Fr trans = fr_sub(zeta, wh_inv);
     Fr acc = fr_zero();
-    air.eval_fold(tl.data(), tn.data(), pub[0], pub[1], first, last, trans, alpha, acc);
+    air.eval_fold(tl.data(), tn.data(), pub, first, last, trans, alpha, acc);
     if (!fr_eq(fr_mul(acc, fr_inv(zh)), quotient)) return 13;
     return 0;
 }

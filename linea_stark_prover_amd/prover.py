@@ -364,6 +364,21 @@ class Context:
                                             for j in range(nc.value)],
                                 details=details, names=names)
 
+    def constraint_degrees(self, air: LineaAIR) -> List[int]:
+        """every constraint's degree under this context's public_degree, in
+        the order of ``air.constraint_names()``: the largest decides the
+        quotient degree, so this finds the constraint behind "quotient degree
+        exceeds the blowup" (lsp_air_constraint_degree; no GPU needed)."""
+        desc = (ctypes.c_int32 * len(air.descriptor()))(*air.descriptor())
+        nc, d = ctypes.c_uint32(), ctypes.c_uint32()
+        L.check(L.lib().lsp_air_num_constraints(desc, len(desc), ctypes.byref(nc)))
+        out = []
+        for j in range(nc.value):
+            L.check(L.lib().lsp_air_constraint_degree(desc, len(desc), self.config.public_degree, j,
+                                                      ctypes.byref(d)))
+            out.append(int(d.value))
+        return out
+
     # ----------------------------------------------------------------- prove
     def prove(self, trace, air: LineaAIR, public_values: np.ndarray, h: Optional[int] = None,
               w: Optional[int] = None, check: bool = False) -> bytes:

@@ -21,6 +21,7 @@ pub mod sys;
 mod dft;
 mod fri;
 mod mmcs;
+pub mod program;
 mod proof;
 
 pub use dft::HipDft;

@@ -383,6 +383,7 @@ pub fn check_constraints(ctx: &Ctx, trace: &p3_matrix::dense::RowMajorMatrix<Val
             sys::LSP_CONSTRAINT_A_INVERSE => "a_inverse",
             sys::LSP_CONSTRAINT_FIRST_ROW => "first_row",
             sys::LSP_CONSTRAINT_TRANSITION => "transition",
+            sys::LSP_CONSTRAINT_PROGRAM => "program assert",
             _ => "last_row",
         };
         let table = if table >= 0 { format!(", table {table}") } else { String::new() };
