@@ -82,8 +82,26 @@ enum { LSP_MEM_HOST = 0, LSP_MEM_DEVICE = 1 };
  * >= w or a PUBLIC k >= npub is LSP_E_ARG too.  Public values stay
  * [alpha, delta, ...]: the built-in configs read the first two, programs any.
  * A descriptor may mix the three types; constraints are numbered and folded
- * in descriptor order, a program's in the order of its ASSERT_ZERO ops. */
-enum { LSP_AIR_PERMUTATION = 1, LSP_AIR_LOOKUP = 2, LSP_AIR_PROGRAM = 3 };
+ * in descriptor order, a program's in the order of its ASSERT_ZERO ops.
+ * LSP_AIR_PROGRAM_PREP: a program that also reads preprocessed columns (p3's
+ * PairBuilder::preprocessed()) -- columns that belong to the AIR, not to the
+ * witness: round constants, selector patterns, the tables of a lookup:
+ *   4, width, prep_width, nslots, nconst, nops, nassert, const[nconst][8], op[nops][4]
+ * It is LSP_AIR_PROGRAM with 1 <= prep_width <= 2^20 and two more operand kinds,
+ *   8 PREP_LOCAL col     9 PREP_NEXT col     (col < prep_width)
+ * the cell of the preprocessed matrix in the row the LOCAL / NEXT operands
+ * read; in the degree rule it counts 1, as a main variable.  Kinds 8 and 9
+ * inside a type-3 config stay LSP_E_ARG.  An AIR that holds a type-4 config
+ * needs a call that is given the preprocessed matrix (lsp_prove_preprocessed,
+ * lsp_verify_preprocessed, lsp_check_constraints_preprocessed,
+ * lsp_quotient_values_preprocessed), whose
+ * width must be at least every prep_width; every other call that takes an AIR
+ * -- lsp_prove, the group and sharded proves, lsp_verify,
+ * lsp_check_constraints, lsp_quotient_values -- answers LSP_E_ARG ("the AIR
+ * reads preprocessed columns").  The descriptor queries (lsp_air_*,
+ * lsp_log_quotient_degree) accept it.  Built-in configs never read
+ * preprocessed columns. */
+enum { LSP_AIR_PERMUTATION = 1, LSP_AIR_LOOKUP = 2, LSP_AIR_PROGRAM = 3, LSP_AIR_PROGRAM_PREP = 4 };
 
 typedef struct lsp_ctx lsp_ctx;
 typedef struct lsp_tree lsp_tree;
@@ -325,6 +343,79 @@ int lsp_check_constraints(lsp_ctx *ctx, const lsp_fr *trace, size_t h, size_t w,
                           const lsp_fr *public_values, size_t npub, int mem, lsp_check_summary *summary,
                           uint64_t *counts, uint64_t *first_rows, lsp_violation *list, size_t cap, size_t *nlist);
 
+/* --------------------------------------------------- preprocessed columns */
+/* Commit an h x wp matrix of fixed columns once (row-major, mem as in the
+ * prove call): its coset LDE with shift GENERATOR, bit-reversed rows,
+ * (h << log_blowup) x wp -- what lsp_coset_lde_batch gives -- is written
+ * straight into a buffer the tree owns and committed as MerkleTreeMmcs::commit
+ * over that single matrix.  *commit_out is the root; *out a tree that
+ * lsp_merkle_open, lsp_merkle_layer and lsp_tree_free serve like any other.
+ * The tree's memory is its own allocation, never the context's pool, so it
+ * outlives any number of other calls on the context: N * wp * 32 bytes of LDE
+ * and (2 N - 1) * 32 bytes of digests, N = h << log_blowup.  The stream is
+ * synchronised before the call returns. */
+int lsp_preprocess(lsp_ctx *ctx, const lsp_fr *cols, size_t h, size_t wp, int mem, lsp_fr *commit_out,
+                   lsp_tree **out);
+/* lsp_quotient_values for an AIR that reads preprocessed columns: prep_lde is
+ * the LDE of the preprocessed matrix in the layout of lde, (h << log_blowup) x
+ * wp (the matrix lsp_preprocess commits); a constraint reads both matrices at
+ * the same two row indices, bitrev_Q(i) for local and bitrev_Q(i + q) for
+ * next.  Through the same stage driver and kernel as a proof's quotient. */
+int lsp_quotient_values_preprocessed(lsp_ctx *ctx, const lsp_fr *lde, size_t h, size_t w, const lsp_fr *prep_lde,
+                                     size_t wp, const int32_t *air, size_t air_len, const lsp_fr *public_values,
+                                     size_t npub, const lsp_fr *alpha, lsp_fr *out, int mem);
+/* The single-context prove call for an AIR with a preprocessed matrix: prep is
+ * any tree of this context (not of another context, on the same device
+ * either: a tree's uploads run on its context's stream, under its context's
+ * mutex) over exactly one matrix of height h << log_blowup
+ * -- lsp_preprocess's, or an lsp_merkle_commit over a caller-made LDE -- and
+ * anything else is LSP_E_ARG, as is an AIR that reads more columns than the
+ * matrix has, or a matrix of more than about 4,400 columns (the alpha powers
+ * of its reduction stay in the workgroup's LDS).  The trace's LDE and tree
+ * cover the witness columns only; the quotient, the opening and the queries
+ * read the tree's matrix where it lies, so one tree serves any number of
+ * proofs.  The proof's bytes are "LSPPRF03" (lsp_verify_preprocessed below
+ * states the protocol); lsp_proof_serialize / lsp_proof_deserialize handle
+ * both formats, and lsp_proof_get_preprocessed_view hands out the openings
+ * lsp_proof_view has no field for.
+ * LSP_CHECK_CONSTRAINTS=1 is not applied here, since the tree holds no raw
+ * columns: call lsp_check_constraints_preprocessed.  One rank only: the group
+ * and sharded proves refuse such an AIR. */
+int lsp_prove_preprocessed(lsp_ctx *ctx, const lsp_fr *trace, size_t h, size_t w, const lsp_tree *prep,
+                           const int32_t *air, size_t air_len, const lsp_fr *public_values, size_t npub, int mem,
+                           lsp_proof **out);
+/* lsp_verify for a proof over an AIR with a preprocessed matrix, whose
+ * commitment (lsp_preprocess's root) and width are the verifier's inputs, as
+ * p3's VerifierData, never proof fields; works on a host-only context.  The
+ * protocol is uni-stark's with one more committed matrix P (h x wp):
+ *   transcript  [log h], trace root, preprocessed root, [public values], alpha
+ *               (the U7/U8/U12 switches act as in lsp_verify; the root's
+ *               position is this library's choice, U13 of DESIGN section 3)
+ *   quotient    constraints read P's LDE at the rows they read the trace's at
+ *   opening     trace at {zeta, zeta w}, chunks at {zeta}, P at {zeta, zeta w};
+ *               the FRI input continues the running alpha_fri power: after the
+ *               2w + q existing terms, wp terms of P at zeta, then wp at zeta w
+ *   queries     a third opening: P's row (wp values) and its path
+ * Wire format "LSPPRF03": LSPPRF02 with u32 prep_width after final_poly_len,
+ * prep@zeta[wp] and prep@zeta*w[wp] after chunks@zeta[q], and per query, after
+ * the quotient row and path, the row[wp] and u32 len + path.  LSPPRF02 bytes
+ * here, and LSPPRF03 bytes in lsp_verify, are LSP_E_VERIFY; a wrong
+ * commitment or width is LSP_E_VERIFY; an AIR that reads more than prep_width
+ * columns is LSP_E_ARG.  tests/preprocessed_ref.py holds an independent
+ * big-integer prover of this protocol; lsp_prove_preprocessed's proofs are
+ * its proofs, byte for byte. */
+int lsp_verify_preprocessed(const lsp_ctx *ctx, const int32_t *air, size_t air_len, const lsp_fr *public_values,
+                            size_t npub, const lsp_fr *prep_commit, uint32_t prep_width, const uint8_t *proof,
+                            size_t len);
+/* lsp_check_constraints for an AIR that reads preprocessed columns: prep is
+ * the raw h x wp matrix (not its LDE), in the same memory as the trace;
+ * PREP_LOCAL / PREP_NEXT read its rows i and (i + 1) mod h.  Outputs, the
+ * device path and the host-only path as in lsp_check_constraints. */
+int lsp_check_constraints_preprocessed(lsp_ctx *ctx, const lsp_fr *trace, size_t h, size_t w, const lsp_fr *prep,
+                                       size_t wp, const int32_t *air, size_t air_len, const lsp_fr *public_values,
+                                       size_t npub, int mem, lsp_check_summary *summary, uint64_t *counts,
+                                       uint64_t *first_rows, lsp_violation *list, size_t cap, size_t *nlist);
+
 /* ------------------------------------------------------------- PCS open */
 /* interpolate_coset [EXT p3-interpolation] of the first h rows of a bit-reversed
  * LDE (the low coset shift*H_h) at z: ys_out gets w values (host memory). */
@@ -526,6 +617,21 @@ typedef struct {
     const lsp_fr *fri_siblings, *fri_paths;        /* num_queries x rounds, num_queries x sum(fri_path_lens) */
 } lsp_proof_view;
 int lsp_proof_get_view(const lsp_proof *proof, lsp_proof_view *view);
+/* The preprocessed openings of an "LSPPRF03" proof, which lsp_proof_view (ABI,
+ * no size field) has no room for: the matrix's width, its opened values at
+ * zeta and zeta*w (width each), and per query its row and path (num_queries x
+ * width, num_queries x path_len).  Pointers live as long as the proof.
+ * LSP_E_STATE on an "LSPPRF02" proof.  lsp_proof_get_view fills its own
+ * fields for either format; a handle rebuilt by lsp_proof_from_view from
+ * that view alone is an LSPPRF02 proof, which no verifier of the AIR accepts:
+ * carry LSPPRF03 proofs as bytes. */
+typedef struct {
+    uint32_t width;
+    const lsp_fr *local, *next;
+    const lsp_fr *rows, *paths;
+    uint32_t path_len;
+} lsp_proof_preprocessed_view;
+int lsp_proof_get_preprocessed_view(const lsp_proof *proof, lsp_proof_preprocessed_view *view);
 /* a proof handle from a view (copies; e.g. a Proof<SC> made elsewhere, for
  * lsp_proof_serialize / lsp_verify); LSP_E_ARG on null or non-canonical data */
 int lsp_proof_from_view(const lsp_proof_view *view, lsp_proof **out);

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("LSP_LIB", os.path.join(_PKG, "_lib", "liblsp_hip.so")
 
 LSP_OK, LSP_E_ARG, LSP_E_OOM, LSP_E_HIP, LSP_E_SIZE, LSP_E_VERIFY, LSP_E_STATE, LSP_E_CONSTRAINT = range(8)
 LSP_MEM_HOST, LSP_MEM_DEVICE = 0, 1
-LSP_AIR_PERMUTATION, LSP_AIR_LOOKUP, LSP_AIR_PROGRAM = 1, 2, 3
+LSP_AIR_PERMUTATION, LSP_AIR_LOOKUP, LSP_AIR_PROGRAM, LSP_AIR_PROGRAM_PREP = 1, 2, 3, 4
 (LSP_CONSTRAINT_B_INVERSE, LSP_CONSTRAINT_A_INVERSE, LSP_CONSTRAINT_FIRST_ROW, LSP_CONSTRAINT_TRANSITION,
  LSP_CONSTRAINT_LAST_ROW, LSP_CONSTRAINT_PROGRAM) = range(6)
 
@@ -61,6 +61,12 @@ class LspViolation(ctypes.Structure):
     """include/lsp.h lsp_violation"""
     _fields_ = [("row", ctypes.c_uint64), ("constraint", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
                 ("value", ctypes.c_uint64 * 4)]
+
+
+class LspProofPrepView(ctypes.Structure):
+    """include/lsp.h lsp_proof_preprocessed_view"""
+    _fields_ = [("width", ctypes.c_uint32), ("local", ctypes.c_void_p), ("next", ctypes.c_void_p),
+                ("rows", ctypes.c_void_p), ("paths", ctypes.c_void_p), ("path_len", ctypes.c_uint32)]
 
 
 class LspError(RuntimeError):
@@ -127,6 +133,9 @@ _SIGS = {
     "lsp_prove": (ctypes.c_int, [ctypes.c_void_p, c_fr_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p,
                                  ctypes.c_size_t, c_fr_p, ctypes.c_size_t, ctypes.c_int,
                                  ctypes.POINTER(ctypes.c_void_p)]),
+    "lsp_prove_preprocessed": (ctypes.c_int, [ctypes.c_void_p, c_fr_p, ctypes.c_size_t, ctypes.c_size_t,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_fr_p,
+                                              ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     "lsp_air_num_constraints": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)]),
     "lsp_air_constraint_degree": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_uint32,
                                                  ctypes.POINTER(ctypes.c_uint32)]),
@@ -138,11 +147,24 @@ _SIGS = {
                                              ctypes.POINTER(LspCheckSummary), ctypes.POINTER(ctypes.c_uint64),
                                              ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(LspViolation),
                                              ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "lsp_preprocess": (ctypes.c_int, [ctypes.c_void_p, c_fr_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, c_fr_p,
+                                      ctypes.POINTER(ctypes.c_void_p)]),
+    "lsp_quotient_values_preprocessed": (ctypes.c_int, [ctypes.c_void_p, c_fr_p, ctypes.c_size_t, ctypes.c_size_t,
+                                                        c_fr_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                                        c_fr_p, ctypes.c_size_t, c_fr_p, c_fr_p, ctypes.c_int]),
+    "lsp_check_constraints_preprocessed": (ctypes.c_int, [ctypes.c_void_p, c_fr_p, ctypes.c_size_t, ctypes.c_size_t,
+                                                          c_fr_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                                          c_fr_p, ctypes.c_size_t, ctypes.c_int,
+                                                          ctypes.POINTER(LspCheckSummary),
+                                                          ctypes.POINTER(ctypes.c_uint64),
+                                                          ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(LspViolation),
+                                                          ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "lsp_proof_serialize": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                            ctypes.POINTER(ctypes.c_size_t)]),
     "lsp_proof_free": (ctypes.c_int, [ctypes.c_void_p]),
     "lsp_proof_deserialize": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]),
     "lsp_proof_get_view": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),  # lsp_proof_view* (proof.py)
+    "lsp_proof_get_preprocessed_view": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),  # LspProofPrepView*
     "lsp_proof_from_view": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "lsp_ctx_attach_comm_ops": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(LspCommOps)]),
     "lsp_comm_rccl_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
@@ -180,6 +202,8 @@ _SIGS = {
                                        ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     "lsp_verify": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_fr_p, ctypes.c_size_t,
                                   ctypes.c_char_p, ctypes.c_size_t]),
+    "lsp_verify_preprocessed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_fr_p, ctypes.c_size_t,
+                                               c_fr_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t]),
     "lsp_last_timings": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
                                         ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t,
                                         ctypes.POINTER(ctypes.c_size_t)]),

@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Tuple, Union
 
 from .field import MODULUS
 
-LSP_AIR_PERMUTATION, LSP_AIR_LOOKUP, LSP_AIR_PROGRAM = 1, 2, 3
+LSP_AIR_PERMUTATION, LSP_AIR_LOOKUP, LSP_AIR_PROGRAM, LSP_AIR_PROGRAM_PREP = 1, 2, 3, 4
 
 
 @dataclass
@@ -109,6 +109,7 @@ class AirLookupConfig:
 # ---------------------------------------------------------------- programs
 # LSP_AIR_PROGRAM (include/lsp.h): operand kinds and opcodes
 (OPND_SLOT, OPND_LOCAL, OPND_NEXT, OPND_PUBLIC, OPND_CONST, OPND_FIRST, OPND_LAST, OPND_TRANS) = range(8)
+OPND_PREP_LOCAL, OPND_PREP_NEXT = 8, 9  # LSP_AIR_PROGRAM_PREP only: a cell of the preprocessed matrix
 OP_ADD, OP_SUB, OP_MUL, OP_ASSERT_ZERO = 1, 2, 3, 4
 MAX_SLOTS = 16
 
@@ -123,13 +124,16 @@ class AirProgramConfig:
     """An LSP_AIR_PROGRAM config in its encoded form: ``ops`` are (opcode, dst,
     a, b) with operands ``kind << 24 | payload``, ``consts`` canonical ints.
     ``desc_width`` bounds the (absolute) column ids; ``ncols`` is what the
-    config adds to ``LineaAIR.width``."""
+    config adds to ``LineaAIR.width``.  ``prep_width`` > 0: the program reads
+    that many preprocessed columns (operand kinds 8 and 9) and encodes as
+    LSP_AIR_PROGRAM_PREP; 0 encodes as LSP_AIR_PROGRAM, exactly as before."""
     desc_width: int
     nslots: int
     consts: List[int]
     ops: List[Tuple[int, int, int, int]]
     ncols: int = -1
     labels: Optional[List[Optional[str]]] = field(default=None, compare=False)
+    prep_width: int = 0
 
     def __post_init__(self):
         if self.ncols < 0:
@@ -149,7 +153,9 @@ class AirProgramConfig:
         return self.ncols
 
     def encode(self) -> List[int]:
-        out = [LSP_AIR_PROGRAM, self.desc_width, self.nslots, len(self.consts), len(self.ops), self.nassert]
+        head = [LSP_AIR_PROGRAM_PREP, self.desc_width, self.prep_width] if self.prep_width else \
+            [LSP_AIR_PROGRAM, self.desc_width]
+        out = head + [self.nslots, len(self.consts), len(self.ops), self.nassert]
         for c in self.consts:
             out += [_i32(c >> (32 * k)) for k in range(8)]
         for o in self.ops:
@@ -210,22 +216,32 @@ class ProgramBuilder:
         b.when_transition().assert_eq(b.next[1], b.local[0] + b.local[1])
         cfg = b.build()
 
+    ``ProgramBuilder(width, preprocessed_width=wp)`` also has
+    ``b.preprocessed[i]`` and ``b.preprocessed_next[i]``, the cells of the wp
+    fixed columns (p3's ``PairBuilder::preprocessed()``) in the rows of
+    ``local`` and ``next``; such a program encodes as LSP_AIR_PROGRAM_PREP.
+
     Equal subexpressions are one node (hash-consing: common-subexpression
     elimination), constants with constants are folded mod r.  ``build()``
     orders each expression so that the side needing more slots runs first
     (Sethi-Ullman), keeps a shared node in its slot until its last use and
     raises ``ValueError`` when more than 16 slots would be live."""
 
-    def __init__(self, width: int):
+    def __init__(self, width: int, preprocessed_width: int = 0):
         if not 1 <= width <= 1 << 20:
             raise ValueError("width outside [1, 2^20]")
+        if not 0 <= preprocessed_width <= 1 << 20:
+            raise ValueError("preprocessed_width outside [0, 2^20]")
         self.width = width
+        self.preprocessed_width = preprocessed_width
         self._nodes: List[Tuple[int, int, int]] = []   # leaves: (-kind - 1, payload, 0); ops: (opcode, a, b)
         self._ids: Dict[Tuple[int, int, int], int] = {}
         self._asserts: List[Tuple[int, Optional[str]]] = []
         self.local = _Vars(self, -OPND_LOCAL - 1, width)
         self.next = _Vars(self, -OPND_NEXT - 1, width)
         self.public = _Vars(self, -OPND_PUBLIC - 1, 1 << 16)
+        self.preprocessed = _Vars(self, -OPND_PREP_LOCAL - 1, preprocessed_width)
+        self.preprocessed_next = _Vars(self, -OPND_PREP_NEXT - 1, preprocessed_width)
         self.is_first_row = Expr(self, self._node(-OPND_FIRST - 1, 0, 0))
         self.is_last_row = Expr(self, self._node(-OPND_LAST - 1, 0, 0))
         self.is_transition = Expr(self, self._node(-OPND_TRANS - 1, 0, 0))
@@ -346,7 +362,8 @@ class ProgramBuilder:
         cl = [0] * len(consts)
         for v, i in consts.items():
             cl[i] = v
-        return AirProgramConfig(self.width, top, cl, ops, ncols, [lab for _, lab in self._asserts])
+        return AirProgramConfig(self.width, top, cl, ops, ncols, [lab for _, lab in self._asserts],
+                                self.preprocessed_width)
 
 
 def _challenge(b: ProgramBuilder, row, ids) -> Expr:
@@ -357,12 +374,14 @@ def _challenge(b: ProgramBuilder, row, ids) -> Expr:
     return acc + b.public[1]
 
 
-def decode_program(it) -> AirProgramConfig:
-    """the words of an LSP_AIR_PROGRAM config after its type word"""
-    width, nslots, nconst, nops, nassert = (next(it) for _ in range(5))
+def decode_program(it, prep: bool = False) -> AirProgramConfig:
+    """the words of an LSP_AIR_PROGRAM (prep: LSP_AIR_PROGRAM_PREP) config after its type word"""
+    width = next(it)
+    prep_width = next(it) if prep else 0
+    nslots, nconst, nops, nassert = (next(it) for _ in range(4))
     consts = [sum((next(it) & 0xFFFFFFFF) << (32 * k) for k in range(8)) for _ in range(nconst)]
     ops = [tuple(next(it) & 0xFFFFFFFF if j >= 2 else next(it) for j in range(4)) for _ in range(nops)]
-    cfg = AirProgramConfig(width, nslots, consts, ops)
+    cfg = AirProgramConfig(width, nslots, consts, ops, prep_width=prep_width)
     if cfg.nassert != nassert:
         raise ValueError("nassert is not the number of ASSERT_ZERO ops")
     return cfg
@@ -427,6 +446,8 @@ class LineaAIR:
                 cfgs.append(AirLookupConfig(a, b, af, bf, ai, bi, oc, next(it)))
             elif t == LSP_AIR_PROGRAM:
                 cfgs.append(decode_program(it))
+            elif t == LSP_AIR_PROGRAM_PREP:
+                cfgs.append(decode_program(it, prep=True))
             else:
                 raise ValueError(f"unknown AIR config type {t}")
         assert next(it, None) is None, "trailing data in AIR descriptor"

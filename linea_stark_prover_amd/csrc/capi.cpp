@@ -499,6 +499,56 @@ int lsp_merkle_commit(lsp_ctx* ctx, const lsp_fr* const* mats, const size_t* wid
     });
 }
 
+int lsp_preprocess(lsp_ctx* ctx, const lsp_fr* cols, size_t h, size_t wp, int mem, lsp_fr* commit_out,
+                   lsp_tree** out) {
+    return guarded(ctx, [&] {
+        LSP_REQUIRE(ctx && cols && commit_out && out, LSP_E_ARG, "bad preprocess arguments");
+        LSP_REQUIRE(wp >= 1 && wp <= (1u << 20), LSP_E_ARG, "preprocessed width outside [1, 2^20]");
+        std::lock_guard<std::mutex> g(ctx->mu);
+        need_gpu(ctx);
+        const uint32_t log_h = log2_exact(h);
+        LSP_REQUIRE(h >= 2 && log_h + ctx->log_blowup <= 40, LSP_E_SIZE, "preprocessed height outside [2, 2^40 / blowup]");
+        const size_t N = h << ctx->log_blowup;
+        // the tree and its device memory, freed on every path out but the last
+        struct Owned {
+            lsp_tree* t = new lsp_tree();
+            ~Owned() {
+                if (!t) return;
+                for (auto* d : t->mats) (void)hipFree(d);
+                (void)hipFree(t->layers);
+                delete t;
+            }
+        } own;
+        lsp_tree* t = own.t;
+        t->ctx = ctx;
+        t->height = N;
+        const Fr* din = dev_in(ctx, cols, h * wp, mem, "api_in");
+        Fr* lde = nullptr;
+        if (hipMalloc(&lde, N * wp * sizeof(Fr)) != hipSuccess) {
+            (void)hipGetLastError();
+            throw LspError(LSP_E_OOM, "hipMalloc of the preprocessed LDE failed");
+        }
+        t->mats.push_back(lde);
+        t->widths.push_back(wp);
+        if (hipMalloc(&t->layers, (2 * N - 1) * sizeof(Fr)) != hipSuccess) {
+            (void)hipGetLastError();
+            t->layers = nullptr;
+            throw LspError(LSP_E_OOM, "hipMalloc of the preprocessed tree failed");
+        }
+        // the LDE goes straight into the tree's buffer: no copy
+        const std::vector<Fr> sh(wp, host_generator());
+        lde_device(ctx, din, h, wp, ctx->log_blowup, sh.data(), lde);
+        MatList m{};
+        m.n = 1;
+        m.ptr[0] = lde;
+        m.width[0] = (uint32_t)wp;
+        *commit_out = from_fr(commit_device(ctx, m, N, t->layers));
+        ctx->sync();  // the host-made tree top goes up asynchronously
+        *out = t;
+        own.t = nullptr;
+    });
+}
+
 int lsp_merkle_open(const lsp_tree* t, size_t index, lsp_fr* rows_out, lsp_fr* path_out) {
     if (!t) return LSP_E_ARG;
     lsp_ctx* ctx = t->ctx;
@@ -604,19 +654,25 @@ int lsp_log_quotient_degree(const int32_t* air, size_t air_len, int32_t public_d
     });
 }
 
-int lsp_quotient_values(lsp_ctx* ctx, const lsp_fr* lde, size_t h, size_t w, const int32_t* air, size_t air_len,
-                        const lsp_fr* pubv, size_t npub, const lsp_fr* alpha, lsp_fr* out, int mem) {
+// lsp_quotient_values, and with a preprocessed LDE (prep_lde, wp) lsp_quotient_values_preprocessed
+extern "C++" {
+namespace {
+int quotient_values(lsp_ctx* ctx, const lsp_fr* lde, size_t h, size_t w, const lsp_fr* prep_lde, size_t wp,
+                    const int32_t* air, size_t air_len, const lsp_fr* pubv, size_t npub, const lsp_fr* alpha,
+                    lsp_fr* out, int mem) {
     return guarded(ctx, [&] {
         LSP_REQUIRE(ctx && alpha && pubv && npub >= 2, LSP_E_ARG, "bad quotient arguments");
+        LSP_REQUIRE(wp <= (1u << 20), LSP_E_ARG, "preprocessed width past 2^20");
         std::lock_guard<std::mutex> g(ctx->mu);
         need_gpu(ctx);
         const Air A = Air::parse(air, air_len);
-        A.require_fits(w, npub);
+        A.require_fits(w, npub, wp);
         const uint32_t log_h = log2_exact(h), log_q = A.log_quotient_degree(ctx->public_degree);
         const uint32_t logQ = log_h + log_q;
         LSP_REQUIRE(log_q <= ctx->log_blowup, LSP_E_ARG, "quotient degree exceeds the blowup");
         const size_t N = h << ctx->log_blowup, Q = (size_t)1 << logQ;
         const Fr* dlde = dev_in(ctx, lde, N * w, mem, "api_in");
+        const Fr* dprep = wp ? dev_in(ctx, prep_lde, N * wp, mem, "api_prep") : nullptr;
         Fr* dout = dev_out(ctx, out, Q, mem, "api_out");
         QuotientArgs qa;
         const std::vector<Fr> pub = to_frs(pubv, npub);
@@ -626,9 +682,30 @@ int lsp_quotient_values(lsp_ctx* ctx, const lsp_fr* lde, size_t h, size_t w, con
         qa.alpha = to_fr(*alpha);
         qa.out = dout;
         qa.lde_rows = N;
+        if (A.has_prog) {  // (only a program reads it)
+            qa.prep = dprep;
+            qa.wp = (uint32_t)wp;
+        }
         LSP_HIP(launch_quotient(qa, ctx->stream));
         finish_out(ctx, out, dout, Q, mem);
     });
+}
+}  // namespace
+}  // extern "C++"
+
+int lsp_quotient_values(lsp_ctx* ctx, const lsp_fr* lde, size_t h, size_t w, const int32_t* air, size_t air_len,
+                        const lsp_fr* pubv, size_t npub, const lsp_fr* alpha, lsp_fr* out, int mem) {
+    return quotient_values(ctx, lde, h, w, nullptr, 0, air, air_len, pubv, npub, alpha, out, mem);
+}
+
+int lsp_quotient_values_preprocessed(lsp_ctx* ctx, const lsp_fr* lde, size_t h, size_t w, const lsp_fr* prep_lde,
+                                     size_t wp, const int32_t* air, size_t air_len, const lsp_fr* pubv, size_t npub,
+                                     const lsp_fr* alpha, lsp_fr* out, int mem) {
+    if (!prep_lde || wp == 0) {
+        (ctx ? ctx->err : g_err) = "a preprocessed LDE needs a pointer and a width";
+        return LSP_E_ARG;
+    }
+    return quotient_values(ctx, lde, h, w, prep_lde, wp, air, air_len, pubv, npub, alpha, out, mem);
 }
 
 int lsp_interpolate_coset(lsp_ctx* ctx, const lsp_fr* lde_bitrev, size_t h, size_t w, const lsp_fr* shift,
@@ -750,6 +827,21 @@ int lsp_prove(lsp_ctx* ctx, const lsp_fr* trace, size_t h, size_t w, const int32
     });
 }
 
+int lsp_prove_preprocessed(lsp_ctx* ctx, const lsp_fr* trace, size_t h, size_t w, const lsp_tree* prep,
+                           const int32_t* air, size_t air_len, const lsp_fr* pubv, size_t npub, int mem,
+                           lsp_proof** out) {
+    return guarded(ctx, [&] {
+        LSP_REQUIRE(ctx && out && pubv && prep, LSP_E_ARG, "bad prove arguments");
+        std::lock_guard<std::mutex> g(ctx->mu);
+        need_gpu(ctx);
+        const Air A = Air::parse(air, air_len);
+        const std::vector<Fr> pub = to_frs(pubv, npub);
+        const Fr* din = dev_in(ctx, trace, h * w, mem, "trace_in");
+        // (LSP_CHECK_CONSTRAINTS is not applied here: the tree holds the LDE, not the raw columns)
+        *out = prove_device(ctx, din, h, w, A, pub.data(), npub, prep);
+    });
+}
+
 // ---------------------------------------------------- check_constraints
 int lsp_air_num_constraints(const int32_t* air, size_t air_len, uint32_t* n) {
     return guarded(nullptr, [&] {
@@ -780,10 +872,15 @@ int lsp_air_constraint_info(const int32_t* air, size_t air_len, uint32_t j, uint
     });
 }
 
-int lsp_check_constraints(lsp_ctx* ctx, const lsp_fr* trace, size_t h, size_t w, const int32_t* air, size_t air_len,
-                          const lsp_fr* pubv, size_t npub, int mem, lsp_check_summary* summary, uint64_t* counts,
-                          uint64_t* first_rows, lsp_violation* list, size_t cap, size_t* nlist) {
+// lsp_check_constraints, and with the raw preprocessed matrix (prep, wp) lsp_check_constraints_preprocessed
+extern "C++" {
+namespace {
+int check_constraints(lsp_ctx* ctx, const lsp_fr* trace, size_t h, size_t w, const lsp_fr* prep, size_t wp,
+                      const int32_t* air, size_t air_len, const lsp_fr* pubv, size_t npub, int mem,
+                      lsp_check_summary* summary, uint64_t* counts, uint64_t* first_rows, lsp_violation* list,
+                      size_t cap, size_t* nlist) {
     return guarded(ctx, [&] {
+        LSP_REQUIRE(wp <= (1u << 20), LSP_E_ARG, "preprocessed width past 2^20");
         LSP_REQUIRE(ctx && trace && pubv && summary, LSP_E_ARG, "bad check_constraints arguments");
         LSP_REQUIRE(cap == 0 || (list && nlist), LSP_E_ARG, "cap > 0 needs list and nlist");
         LSP_REQUIRE(mem == LSP_MEM_HOST || mem == LSP_MEM_DEVICE, LSP_E_ARG,
@@ -792,7 +889,7 @@ int lsp_check_constraints(lsp_ctx* ctx, const lsp_fr* trace, size_t h, size_t w,
         LSP_REQUIRE(h && !(h & (h - 1)), LSP_E_ARG, "trace height must be a power of two");
         std::lock_guard<std::mutex> g(ctx->mu);
         const Air A = Air::parse(air, air_len);
-        A.require_fits(w, npub);
+        A.require_fits(w, npub, wp);
         const std::vector<Fr> pub = to_frs(pubv, npub);
         CheckReport r;
         if (ctx->device == LSP_HOST_ONLY && mem == LSP_MEM_HOST) {
@@ -800,11 +897,14 @@ int lsp_check_constraints(lsp_ctx* ctx, const lsp_fr* trace, size_t h, size_t w,
             static_assert(sizeof(Fr) == sizeof(lsp_fr), "lsp_fr is Fr's words");
             std::vector<Fr> t(h * w);
             std::memcpy(t.data(), trace, t.size() * sizeof(Fr));
-            r = check_constraints_host(t.data(), h, w, A, pub.data(), npub, cap);
+            std::vector<Fr> pm(h * wp);
+            if (wp) std::memcpy(pm.data(), prep, pm.size() * sizeof(Fr));
+            r = check_constraints_host(t.data(), h, w, A, pub.data(), npub, cap, wp ? pm.data() : nullptr, wp);
         } else {
             need_gpu(ctx);
             const Fr* din = dev_in(ctx, trace, h * w, mem, "trace_in");
-            r = check_constraints_device(ctx, din, h, w, A, pub.data(), npub, cap);
+            const Fr* dprep = wp ? dev_in(ctx, prep, h * wp, mem, "prep_in") : nullptr;
+            r = check_constraints_device(ctx, din, h, w, A, pub.data(), npub, cap, dprep, wp);
         }
         *summary = r.s;
         if (counts) std::copy(r.counts.begin(), r.counts.end(), counts);
@@ -812,6 +912,27 @@ int lsp_check_constraints(lsp_ctx* ctx, const lsp_fr* trace, size_t h, size_t w,
         if (nlist) *nlist = r.list.size();
         if (cap) std::copy(r.list.begin(), r.list.end(), list);
     });
+}
+}  // namespace
+}  // extern "C++"
+
+int lsp_check_constraints(lsp_ctx* ctx, const lsp_fr* trace, size_t h, size_t w, const int32_t* air, size_t air_len,
+                          const lsp_fr* pubv, size_t npub, int mem, lsp_check_summary* summary, uint64_t* counts,
+                          uint64_t* first_rows, lsp_violation* list, size_t cap, size_t* nlist) {
+    return check_constraints(ctx, trace, h, w, nullptr, 0, air, air_len, pubv, npub, mem, summary, counts, first_rows,
+                             list, cap, nlist);
+}
+
+int lsp_check_constraints_preprocessed(lsp_ctx* ctx, const lsp_fr* trace, size_t h, size_t w, const lsp_fr* prep,
+                                       size_t wp, const int32_t* air, size_t air_len, const lsp_fr* pubv, size_t npub,
+                                       int mem, lsp_check_summary* summary, uint64_t* counts, uint64_t* first_rows,
+                                       lsp_violation* list, size_t cap, size_t* nlist) {
+    if (!prep || wp == 0) {
+        (ctx ? ctx->err : g_err) = "a preprocessed matrix needs a pointer and a width";
+        return LSP_E_ARG;
+    }
+    return check_constraints(ctx, trace, h, w, prep, wp, air, air_len, pubv, npub, mem, summary, counts, first_rows,
+                             list, cap, nlist);
 }
 
 // ------------------------------------------------------- sharded prove
@@ -859,6 +980,8 @@ int lsp_prove_group(lsp_group* grp, const lsp_fr* const* traces, size_t h, size_
         LSP_REQUIRE(grp && traces && out && pubv, LSP_E_ARG, "bad prove_group arguments");
         const int G = (int)grp->ctxs.size();
         const Air A = Air::parse(air, air_len);
+        LSP_REQUIRE(A.prep_width == 0, LSP_E_ARG,
+                    "the AIR reads preprocessed columns: the group prove has no preprocessed matrix");
         const std::vector<Fr> pub = to_frs(pubv, npub);
         ThreadGroup tg(G);
         for (int r = 0; r < G; ++r) tg.device[r] = grp->ctxs[r]->device;
@@ -1141,6 +1264,14 @@ int lsp_proof_get_view(const lsp_proof* p, lsp_proof_view* view) {
     });
 }
 
+int lsp_proof_get_preprocessed_view(const lsp_proof* p, lsp_proof_preprocessed_view* view) {
+    return guarded(nullptr, [&] {
+        LSP_REQUIRE(p && view, LSP_E_ARG, "null argument");
+        LSP_REQUIRE(!p->rehearsal, LSP_E_STATE, "a rehearsal proof holds fabricated data");
+        proof_prep_view(*p, view);
+    });
+}
+
 int lsp_proof_from_view(const lsp_proof_view* view, lsp_proof** out) {
     return guarded(nullptr, [&] {
         LSP_REQUIRE(view && out, LSP_E_ARG, "null");
@@ -1160,8 +1291,31 @@ int lsp_verify(const lsp_ctx* ctx, const int32_t* air, size_t air_len, const lsp
     int g = guarded(nullptr, [&] {
         LSP_REQUIRE(ctx && pubv && proof, LSP_E_ARG, "bad verify arguments");
         const Air A = Air::parse(air, air_len);
+        LSP_REQUIRE(A.prep_width == 0, LSP_E_ARG,
+                    "the AIR reads preprocessed columns: this call has no preprocessed commitment");
         const std::vector<Fr> pub = to_frs(pubv, npub);
         const int v = verify_host(ctx, A, pub.data(), npub, proof, len);
+        if (v != 0) {
+            g_err = "proof rejected at check " + std::to_string(v);
+            rc = LSP_E_VERIFY;
+        }
+    });
+    return g != LSP_OK ? g : rc;
+}
+
+int lsp_verify_preprocessed(const lsp_ctx* ctx, const int32_t* air, size_t air_len, const lsp_fr* pubv, size_t npub,
+                            const lsp_fr* prep_commit, uint32_t prep_width, const uint8_t* proof, size_t len) {
+    int rc = LSP_OK;
+    int g = guarded(nullptr, [&] {
+        LSP_REQUIRE(ctx && pubv && proof && prep_commit, LSP_E_ARG, "bad verify arguments");
+        LSP_REQUIRE(prep_width >= 1 && prep_width <= (1u << 20), LSP_E_ARG, "preprocessed width outside [1, 2^20]");
+        const Air A = Air::parse(air, air_len);
+        LSP_REQUIRE(A.prep_width <= prep_width, LSP_E_ARG,
+                    "the AIR reads " + std::to_string(A.prep_width) + " preprocessed columns of " +
+                        std::to_string(prep_width));
+        const std::vector<Fr> pub = to_frs(pubv, npub);
+        const Fr root = to_fr(*prep_commit);
+        const int v = verify_host(ctx, A, pub.data(), npub, proof, len, &root, prep_width);
         if (v != 0) {
             g_err = "proof rejected at check " + std::to_string(v);
             rc = LSP_E_VERIFY;

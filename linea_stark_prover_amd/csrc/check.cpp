@@ -21,15 +21,16 @@ void summarise(CheckReport& r) {
     }
 }
 
-void check_shape(size_t h, size_t w, const Air& air, size_t npub) {
-    air.require_fits(w, npub);
+void check_shape(size_t h, size_t w, const Air& air, size_t npub, const Fr* prep, size_t wp) {
+    LSP_REQUIRE((prep != nullptr) == (wp != 0), LSP_E_ARG, "a preprocessed matrix needs a pointer and a width");
+    air.require_fits(w, npub, wp);
     (void)log2_exact(h);
 }
 }  // namespace
 
 CheckReport check_constraints_host(const Fr* trace, size_t h, size_t w, const Air& air, const Fr* pub, size_t npub,
-                                   size_t cap) {
-    check_shape(h, w, air, npub);
+                                   size_t cap, const Fr* prep, size_t wp) {
+    check_shape(h, w, air, npub, prep, wp);
     CheckReport r;
     const uint32_t nc = air.num_constraints();
     r.s = lsp_check_summary{0, 0, UINT64_MAX, UINT32_MAX, nc};
@@ -39,7 +40,8 @@ CheckReport check_constraints_host(const Fr* trace, size_t h, size_t w, const Ai
     std::vector<Fr> vals(nc);
     for (size_t i = 0; i < h; ++i) {
         const Fr* loc = trace + i * w;
-        const Fr* nxt = trace + (i + 1 == h ? 0 : i + 1) * w;
+        const size_t in = i + 1 == h ? 0 : i + 1;
+        const Fr* nxt = trace + in * w;
         const bool last = i + 1 == h;
         uint32_t j = 0;
         bool any = false;
@@ -52,7 +54,8 @@ CheckReport check_constraints_host(const Fr* trace, size_t h, size_t w, const Ai
                          r.first_rows[j] = std::min<uint64_t>(r.first_rows[j], i);
                      }
                      ++j;
-                 });
+                 },
+                 prep ? prep + i * wp : nullptr, prep ? prep + in * wp : nullptr);
         if (!any) continue;
         ++r.s.failed_rows;
         for (uint32_t k = 0; k < nc && r.list.size() < cap; ++k)
@@ -63,8 +66,8 @@ CheckReport check_constraints_host(const Fr* trace, size_t h, size_t w, const Ai
 }
 
 CheckReport check_constraints_device(lsp_ctx* ctx, const Fr* d_trace, size_t h, size_t w, const Air& air,
-                                     const Fr* pub, size_t npub, size_t cap) {
-    check_shape(h, w, air, npub);
+                                     const Fr* pub, size_t npub, size_t cap, const Fr* d_prep, size_t wp) {
+    check_shape(h, w, air, npub, d_prep, wp);
     CheckReport r;
     const uint32_t nc = air.num_constraints();
     r.s = lsp_check_summary{0, 0, UINT64_MAX, UINT32_MAX, nc};
@@ -92,6 +95,8 @@ CheckReport check_constraints_device(lsp_ctx* ctx, const Fr* d_trace, size_t h, 
         a.npub = (uint32_t)npub;
         a.prog = 1;
         a.prog_slots = air.prog_slots;
+        a.prep = d_prep;
+        a.wp = (uint32_t)wp;
     }
     a.row_mask = mask;
     a.count = cnt;

@@ -190,11 +190,19 @@ Fr P2Host::hash(const Fr* in, size_t n) const {
 // kernel later indexes with -- slots, constants, columns, public values -- is
 // checked here or in require_fits, and a slot is read only after an earlier op
 // wrote it, so no evaluator ever sees an undefined register.
+// prep: an LSP_AIR_PROGRAM_PREP config -- prep_width follows width, and the
+// operand kinds PREP_LOCAL / PREP_NEXT exist.  Its device form is a plain
+// program's (type word 3, no prep_width: the kernels take the matrix's width
+// from the launch), so both types share the interpreter.
 template <class Next>
-static void parse_program(Air& air, AirCfg& g, Next&& next, size_t cfg) {
-    const int32_t width = next(), nslots = next(), nconst = next(), nops = next(), nassert = next();
+static void parse_program(Air& air, AirCfg& g, Next&& next, size_t cfg, bool prep) {
+    const int32_t width = next(), prep_width = prep ? next() : 0;
+    const int32_t nslots = next(), nconst = next(), nops = next(), nassert = next();
     const std::string where = "AIR program (config " + std::to_string(cfg) + ")";
     LSP_REQUIRE(width >= 1 && width <= (1 << 20), LSP_E_ARG, where + ": bad width");
+    LSP_REQUIRE(!prep || (prep_width >= 1 && prep_width <= (1 << 20)), LSP_E_ARG,
+                where + ": preprocessed width outside [1, 2^20]");
+    air.prep_width = std::max(air.prep_width, (uint32_t)prep_width);
     LSP_REQUIRE(nslots >= 0 && nslots <= (int32_t)AIR_PROG_MAX_SLOTS, LSP_E_ARG, where + ": more than 16 slots");
     LSP_REQUIRE(nconst >= 0 && nconst <= (1 << 16), LSP_E_ARG, where + ": more than 2^16 constants");
     LSP_REQUIRE(nops >= 1 && nops <= (1 << 20), LSP_E_ARG, where + ": op count outside [1, 2^20]");
@@ -244,6 +252,12 @@ static void parse_program(Air& air, AirCfg& g, Next&& next, size_t cfg) {
                 case AIR_OPND_LAST:
                 case AIR_OPND_TRANS:
                     LSP_REQUIRE(v == 0, LSP_E_ARG, op + ": selector operand with a payload");
+                    break;
+                case AIR_OPND_PREP_LOCAL:
+                case AIR_OPND_PREP_NEXT:
+                    LSP_REQUIRE(prep, LSP_E_ARG, op + ": unknown operand kind (preprocessed cells need config type 4)");
+                    LSP_REQUIRE(v < (uint32_t)prep_width, LSP_E_ARG,
+                                op + ": column outside the program's preprocessed width");
                     break;
                 default: throw LspError(LSP_E_ARG, op + ": unknown operand kind");
             }
@@ -310,22 +324,27 @@ Air Air::parse(const int32_t* d, size_t n) {
             for (int32_t t = 0; t < g.ntab; ++t) g.b_inv.push_back(col());
             for (int32_t t = 0; t < g.ntab; ++t) g.occ.push_back(col());
             g.check = col();
-        } else if (g.type == LSP_AIR_PROGRAM) {
-            parse_program(air, g, next, (size_t)c);  // (appends its device form to air.dev)
+        } else if (g.is_prog()) {
+            // (appends its device form to air.dev)
+            parse_program(air, g, next, (size_t)c, g.type == LSP_AIR_PROGRAM_PREP);
             air.has_prog = true;
             air.prog_slots = std::max(air.prog_slots, g.nslots);
         } else {
             throw LspError(LSP_E_ARG, "unknown AIR config type");
         }
-        if (g.type != LSP_AIR_PROGRAM) air.dev.insert(air.dev.end(), d + p0, d + p);
+        if (!g.is_prog()) air.dev.insert(air.dev.end(), d + p0, d + p);
         air.cfgs.push_back(std::move(g));
     }
     LSP_REQUIRE(p == n, LSP_E_ARG, "trailing data in AIR descriptor");
     return air;
 }
 
-void Air::require_fits(size_t w, size_t npub) const {
+void Air::require_fits(size_t w, size_t npub, size_t wp) const {
     LSP_REQUIRE(npub >= 2, LSP_E_ARG, "public values must hold [alpha, delta]");
+    LSP_REQUIRE(prep_width == 0 || wp != 0, LSP_E_ARG,
+                "the AIR reads preprocessed columns: this call has no preprocessed matrix");
+    LSP_REQUIRE(prep_width <= wp, LSP_E_ARG,
+                "the AIR reads " + std::to_string(prep_width) + " preprocessed columns of " + std::to_string(wp));
     LSP_REQUIRE(max_col < w, LSP_E_ARG, "AIR column id outside the trace width");
     LSP_REQUIRE(max_pub < (int64_t)npub, LSP_E_ARG,
                 "AIR program reads public value " + std::to_string(max_pub) + " of " + std::to_string(npub));
@@ -348,6 +367,8 @@ static void program_degrees(const AirCfg& g, int pd, std::vector<int>& out) {
             case AIR_OPND_SLOT: return slot[(uint32_t)x & 0xffffffu];
             case AIR_OPND_LOCAL:
             case AIR_OPND_NEXT:
+            case AIR_OPND_PREP_LOCAL:  // a preprocessed variable counts as a main one
+            case AIR_OPND_PREP_NEXT:
             case AIR_OPND_FIRST:
             case AIR_OPND_LAST: return 1;
             case AIR_OPND_PUBLIC: return pd;
@@ -369,7 +390,7 @@ static void program_degrees(const AirCfg& g, int pd, std::vector<int>& out) {
 std::vector<int> Air::degrees(int pd) const {
     std::vector<int> out;
     for (const auto& g : cfgs) {
-        if (g.type == LSP_AIR_PROGRAM) {
+        if (g.is_prog()) {
             program_degrees(g, pd, out);
         } else if (g.type == LSP_AIR_PERMUTATION) {
             const int a = std::max(horner_deg(g.a.size(), pd), pd), b = std::max(horner_deg(g.b.size(), pd), pd);
@@ -388,7 +409,7 @@ std::vector<int> Air::degrees(int pd) const {
 std::pair<int, int> Air::stats(int pd) const {
     int maxd = 0, k = 0;
     for (const auto& g : cfgs) {
-        if (g.type == LSP_AIR_PROGRAM) {
+        if (g.is_prog()) {
             std::vector<int> dg;
             program_degrees(g, pd, dg);
             for (int x : dg) maxd = std::max(maxd, x);
@@ -418,15 +439,15 @@ uint32_t Air::log_quotient_degree(int pd) const {
 }
 
 void Air::eval_fold(const Fr* loc, const Fr* nxt, const Fr* pub, const Fr& first, const Fr& last, const Fr& trans,
-                    const Fr& al, Fr& acc) const {
-    eval(loc, nxt, pub, first, last, trans, [&](const Fr& x) { acc = fr_add(fr_mul(acc, al), x); });
+                    const Fr& al, Fr& acc, const Fr* ploc, const Fr* pnxt) const {
+    eval(loc, nxt, pub, first, last, trans, [&](const Fr& x) { acc = fr_add(fr_mul(acc, al), x); }, ploc, pnxt);
 }
 
 Air::ConsInfo Air::constraint_info(uint32_t j) const {
     uint32_t k = 0;
     for (size_t c = 0; c < cfgs.size(); ++c) {
         const AirCfg& g = cfgs[c];
-        const uint32_t n = g.type == LSP_AIR_PROGRAM       ? g.nassert
+        const uint32_t n = g.is_prog()                     ? g.nassert
                            : g.type == LSP_AIR_PERMUTATION ? 4
                                                            : 4 + (uint32_t)g.ntab;
         if (j >= k + n) {
@@ -435,7 +456,7 @@ Air::ConsInfo Air::constraint_info(uint32_t j) const {
         }
         const uint32_t i = j - k;
         ConsInfo o{(uint32_t)c, g.type, 0, -1};
-        if (g.type == LSP_AIR_PROGRAM) {
+        if (g.is_prog()) {
             o.kind = LSP_CONSTRAINT_PROGRAM;
         } else if (g.type == LSP_AIR_PERMUTATION) {
             static const int32_t kinds[4] = {LSP_CONSTRAINT_B_INVERSE, LSP_CONSTRAINT_FIRST_ROW,

@@ -217,13 +217,16 @@ struct Challenger {
 // LSP_AIR_PROGRAM operands and opcodes (include/lsp.h)
 enum : uint32_t {
     AIR_OPND_SLOT = 0, AIR_OPND_LOCAL = 1, AIR_OPND_NEXT = 2, AIR_OPND_PUBLIC = 3, AIR_OPND_CONST = 4,
-    AIR_OPND_FIRST = 5, AIR_OPND_LAST = 6, AIR_OPND_TRANS = 7
+    AIR_OPND_FIRST = 5, AIR_OPND_LAST = 6, AIR_OPND_TRANS = 7,
+    // LSP_AIR_PROGRAM_PREP only: a cell of the preprocessed matrix
+    AIR_OPND_PREP_LOCAL = 8, AIR_OPND_PREP_NEXT = 9
 };
 enum : int32_t { AIR_OP_ADD = 1, AIR_OP_SUB = 2, AIR_OP_MUL = 3, AIR_OP_ASSERT_ZERO = 4 };
 constexpr uint32_t AIR_PROG_MAX_SLOTS = 16;
 
 struct AirCfg {
-    int type;  // 1 perm, 2 lookup, 3 program
+    int type;  // 1 perm, 2 lookup, 3 program, 4 program that reads preprocessed columns
+    bool is_prog() const { return type == LSP_AIR_PROGRAM || type == LSP_AIR_PROGRAM_PREP; }
     std::vector<int32_t> a, b;             // perm: a, b ; lookup: a, flattened b tables
     int32_t binv = 0, check = 0;           // perm
     int32_t ntab = 0, nbc = 0, a_filter = 0, a_inv = 0;
@@ -244,10 +247,16 @@ struct Air {
     bool has_prog = false;
     uint32_t prog_slots = 0;
     int64_t max_pub = -1;
+    // the largest prep_width among the LSP_AIR_PROGRAM_PREP configs (0: the AIR
+    // reads no preprocessed column); every PREP_LOCAL / PREP_NEXT column is
+    // below its own config's prep_width (parse), hence below this
+    uint32_t prep_width = 0;
     std::vector<int32_t> dev;
     static Air parse(const int32_t* d, size_t n);
-    // what only a call knows: every column id < w, every public index < npub
-    void require_fits(size_t w, size_t npub) const;
+    // what only a call knows: every column id < w, every public index < npub,
+    // and the preprocessed matrix is at least prep_width wide (wp = 0: the
+    // call has none, so an AIR that reads one is refused)
+    void require_fits(size_t w, size_t npub, size_t wp = 0) const;
     // every constraint's degree under the U6 public-degree rule, in eval's order
     std::vector<int> degrees(int public_degree) const;
     // (max constraint degree, constraint count) under the U6 public-degree rule
@@ -256,13 +265,14 @@ struct Air {
     // LineaAIR::eval on concrete values: push(x) gets every constraint's value
     // (already multiplied by its selector) in eval's order.  pub = [alpha,
     // delta, ...]: programs read any of them (require_fits has checked their
-    // indices) and take the selectors as operands like any other
+    // indices) and take the selectors as operands like any other.  ploc / pnxt:
+    // the same two rows of the preprocessed matrix (none: the AIR reads none)
     template <class Push>
     void eval(const Fr* loc, const Fr* nxt, const Fr* pub, const Fr& first, const Fr& last, const Fr& trans,
-              Push&& push) const;
+              Push&& push, const Fr* ploc = nullptr, const Fr* pnxt = nullptr) const;
     // concrete evaluation folded into acc (verifier / tests)
     void eval_fold(const Fr* loc, const Fr* nxt, const Fr* pub, const Fr& first, const Fr& last, const Fr& trans,
-                   const Fr& alpha, Fr& acc) const;
+                   const Fr& alpha, Fr& acc, const Fr* ploc = nullptr, const Fr* pnxt = nullptr) const;
     // what constraint j of eval's order is (lsp_air_constraint_info); LSP_E_ARG when j is past the end
     struct ConsInfo {
         uint32_t config;
@@ -280,11 +290,11 @@ inline Fr air_horner(const Fr* row, const int32_t* ids, size_t n, const Fr& a) {
 
 template <class Push>
 void Air::eval(const Fr* loc, const Fr* nxt, const Fr* pub, const Fr& first, const Fr& last, const Fr& trans,
-               Push&& push) const {
+               Push&& push, const Fr* ploc, const Fr* pnxt) const {
     const Fr one = fr_one();
     const Fr &ap = pub[0], &dl = pub[1];
     for (const auto& g : cfgs) {
-        if (g.type == LSP_AIR_PROGRAM) {
+        if (g.is_prog()) {
             Fr slot[AIR_PROG_MAX_SLOTS];
             auto opnd = [&](int32_t x) -> Fr {
                 const uint32_t k = (uint32_t)x >> 24, v = (uint32_t)x & 0xffffffu;
@@ -296,6 +306,8 @@ void Air::eval(const Fr* loc, const Fr* nxt, const Fr* pub, const Fr& first, con
                     case AIR_OPND_CONST: return g.pconst[v];
                     case AIR_OPND_FIRST: return first;
                     case AIR_OPND_LAST: return last;
+                    case AIR_OPND_PREP_LOCAL: return ploc[v];
+                    case AIR_OPND_PREP_NEXT: return pnxt[v];
                     default: return trans;
                 }
             };
@@ -337,6 +349,7 @@ void Air::eval(const Fr* loc, const Fr* nxt, const Fr* pub, const Fr& first, con
 struct lsp_query {
     std::vector<Fr> trow, tpath, qrow, qpath, sib;
     std::vector<std::vector<Fr>> fpath;
+    std::vector<Fr> prow, ppath;  // the preprocessed matrix's opening (LSPPRF03 only)
 };
 
 }  // namespace lsp
@@ -345,6 +358,10 @@ struct lsp_proof {
     uint32_t log_h = 0, log_q = 0, w = 0;
     lsp::Fr troot, qroot, pow_w;
     std::vector<lsp::Fr> tl, tn, qc, roots, final_poly;
+    // a proof over an AIR with a preprocessed matrix (wire format "LSPPRF03"):
+    // its width (0: none, "LSPPRF02") and its opened values at zeta and zeta w
+    uint32_t wp = 0;
+    std::vector<lsp::Fr> pl, pn;
     std::vector<lsp::lsp_query> queries;
     // made under a rehearsal transport (lsp_ctx_attach_loopback): peers' data
     // fabricated, so not a proof -- serialize / view refuse it (shape queries only)
@@ -354,6 +371,7 @@ struct lsp_proof {
     mutable std::mutex cache_mu;
     mutable std::vector<uint8_t> wire;  // serialize() result, cached by lsp_proof_serialize
     mutable std::shared_ptr<void> view_cache;  // flat arrays behind lsp_proof_view (proof.cpp)
+    mutable std::shared_ptr<void> prep_view_cache;  // ... behind lsp_proof_preprocessed_view
 };
 
 // a parsed CBOR RawPermutationTrace / RawLookupTrace (cbor.cpp)

@@ -8,6 +8,9 @@
 // form, canonical -- so a constant operand is nine scalar loads and no
 // conversion:
 //   3, width, nslots, nconst, nops, nassert, const[nconst][9], op[nops][4]
+// An LSP_AIR_PROGRAM_PREP config takes the same form (type word 3, prep_width
+// dropped): its PREP_LOCAL / PREP_NEXT operands read the preprocessed matrix
+// of the launch, whose width the host has checked against every prep_width.
 //
 // Register file: LDS, not an indexed local array (the compiler sends a
 // runtime-indexed array to scratch).  Limb-planar: slot s, limb l of thread t
@@ -22,7 +25,8 @@
 // are scalar loads.
 //
 // Bounds of the arithmetic (Q29 of the two kernels, fr29.hpp).  An operand is
-//   a loaded cell or public value   f29_from_fr: normalised, < 2 r
+//   a loaded cell or public value   f29_from_fr: normalised, < 2 r (a cell of
+//                                   the trace or of the preprocessed matrix)
 //   a constant                      canonical: normalised, < r
 //   a selector                      the quotient's are products (< 8.92 r) or
 //                                   x - w^-1 (< 2 r); the check's are 0 or 1
@@ -50,6 +54,11 @@ struct ProgEnv {
     F29 first, last, trans;  // the selector operands
     uint32_t* regs;      // the block's register file
     uint32_t lds_slots;  // slots it was sized for
+    // the same two rows of the preprocessed matrix (wp = 0: none; the host
+    // refuses an AIR that reads one where the call has none)
+    const Fr* ploc;
+    const Fr* pnxt;
+    uint32_t wp;
 };
 
 __device__ __forceinline__ F29 prog_slot_ld(const ProgEnv& e, uint32_t s) {
@@ -86,6 +95,8 @@ __device__ __forceinline__ F29 prog_operand(const ProgEnv& e, const int32_t* __r
         }
         case 5: return e.first;
         case 6: return e.last;
+        case 8: return LSP_BOUNDS(v < e.wp) ? f29_from_fr(e.ploc[v]) : f29_zero();
+        case 9: return LSP_BOUNDS(v < e.wp) ? f29_from_fr(e.pnxt[v]) : f29_zero();
         default: return e.trans;
     }
 }

@@ -78,6 +78,8 @@ __device__ __forceinline__ bool f29_is_zero_mod_r(const F29& v) {
 
 // LineaAIR::eval on one row pair: push(value, selector) per constraint in
 // eval's order, value normalised and < 2 r, not multiplied by the selector.
+// i, in: the rows `loc` and `nxt` are (a program reads the preprocessed matrix
+// at the same two).
 // PROG: also run LSP_AIR_PROGRAM configs (k_air_prog.hpp; an instantiation of
 // its own, as in k_quotient.hip).  A program takes the 0/1 selectors as data
 // wherever it names them, so its asserts are pushed under `always`; an asserted
@@ -85,7 +87,8 @@ __device__ __forceinline__ bool f29_is_zero_mod_r(const F29& v) {
 // through one reduction first (normalised, < 2 r: what the zero test needs).
 template <bool PROG, class Push>
 __device__ __forceinline__ void check_walk(const Q29& F, const CheckArgs& a, const Fr* __restrict__ loc,
-                                           const Fr* __restrict__ nxt, bool first, bool last, Push&& push) {
+                                           const Fr* __restrict__ nxt, uint64_t i, uint64_t in, bool first, bool last,
+                                           Push&& push) {
     const bool trans = !last, always = true;
     const F29 one = f29_from_fr(fr_one());
     const F29 ap = f29_from_fr(a.pub_alpha), dl = f29_from_fr(a.pub_delta);
@@ -144,8 +147,19 @@ __device__ __forceinline__ void check_walk(const Q29& F, const CheckArgs& a, con
         } else if constexpr (PROG) {
             extern __shared__ uint32_t prog_regs[];
             const F29 zero = f29_zero();
-            const ProgEnv e{loc,         nxt, a.w, a.pub, a.npub, first ? one : zero, last ? one : zero,
-                            trans ? one : zero, prog_regs, a.prog_slots};
+            const ProgEnv e{loc,
+                            nxt,
+                            a.w,
+                            a.pub,
+                            a.npub,
+                            first ? one : zero,
+                            last ? one : zero,
+                            trans ? one : zero,
+                            prog_regs,
+                            a.prog_slots,
+                            a.prep + i * a.wp,  // (rows i and in of the h x wp matrix)
+                            a.prep + in * a.wp,
+                            a.wp};
             p = air_prog_run(F, e, d, p, [&](const F29& v) { push(f29_reduce_qt(v, F.qt), always); });
         }
     }
@@ -172,7 +186,7 @@ __global__ __launch_bounds__(256) void k_check(CheckArgs a) {
     unsigned long long* first_row = reinterpret_cast<unsigned long long*>(a.first_row);
     uint32_t j = 0;
     bool any = false;
-    check_walk<PROG>(F, a, loc, nxt, i == 0, i + 1 == a.h, [&](const F29& v, bool sel) {
+    check_walk<PROG>(F, a, loc, nxt, i, in, i == 0, i + 1 == a.h, [&](const F29& v, bool sel) {
         const bool bad = live && sel && !f29_is_zero_mod_r(v);
         const unsigned long long m = __ballot(bad);
         any |= bad;
@@ -201,7 +215,8 @@ __global__ __launch_bounds__(64) void k_check_rows(CheckArgs a) {
     }
     const uint64_t in = i + 1 == a.h ? 0 : i + 1;
     uint32_t j = 0;
-    check_walk<PROG>(F, a, a.trace + i * a.w, a.trace + in * a.w, i == 0, i + 1 == a.h, [&](const F29& v, bool sel) {
+    check_walk<PROG>(F, a, a.trace + i * a.w, a.trace + in * a.w, i, in, i == 0, i + 1 == a.h,
+                     [&](const F29& v, bool sel) {
         const Fr x = f29_to_fr_qt(v, qt);  // canonical, ark form
         if (live && LSP_BOUNDS(j < a.ncons)) a.vals[t * a.ncons + j] = sel ? x : fr_zero();
         ++j;
@@ -211,6 +226,7 @@ __global__ __launch_bounds__(64) void k_check_rows(CheckArgs a) {
 
 hipError_t launch_check(const CheckArgs& a, hipStream_t st) {
     if (!a.h || !a.row_mask || !a.count || !a.first_row) return hipErrorInvalidValue;
+    if (a.wp && (!a.prep || !a.prog)) return hipErrorInvalidValue;
     if (a.prog) {
         if (!a.pub || a.npub < 2 || a.prog_slots > 16) return hipErrorInvalidValue;
         const uint32_t bs = air_prog_block(a.prog_slots);
@@ -229,6 +245,7 @@ hipError_t launch_check(const CheckArgs& a, hipStream_t st) {
 
 hipError_t launch_check_rows(const CheckArgs& a, hipStream_t st) {
     if (!a.h || !a.nrows || !a.rows || !a.vals) return hipErrorInvalidValue;
+    if (a.wp && (!a.prep || !a.prog)) return hipErrorInvalidValue;
     if (a.prog) {  // 64 threads: 16 slots are 36 KB
         if (!a.pub || a.npub < 2 || a.prog_slots > 16) return hipErrorInvalidValue;
         hipLaunchKernelGGL(k_check_rows<true>, dim3(nblocks(a.nrows, 64)), dim3(64),

@@ -195,6 +195,55 @@ __global__ __launch_bounds__(256) void k_reduce_rows(ReduceArgs a) {
     a.out[i] = fr_reduce_once(f29_repack_out(f29_reduce_qt(f29_lazy3(t1, t2, t3), qt)));  // < 24.3 r in
 }
 
+// The preprocessed matrix's two terms of the FRI input, added to what
+// k_reduce_rows wrote (PrepReduceArgs, kernels.hpp).  As there: the alpha
+// powers once per workgroup into LDS in the 29-bit form, the row's elements
+// (ark form) times them on the 29-bit product, at most RR_CHUNK products per
+// lazy sum, the next chunk of the row requested before the current chunk's
+// products.  Bounds: rr < 2 r; ry - rr through f29_sub16 < 17 r; times an
+// inverse denominator (< 2 r) < 8.1 r; times the offset (< 2 r) < 8.1 r; two
+// such terms and the old value (canonical) < 17.2 r into f29_reduce_qt.
+__global__ __launch_bounds__(256) void k_reduce_prep(PrepReduceArgs a) {
+    extern __shared__ uint4 rp_lds[];
+    uint4* qt = rp_lds;  // 3 * F29_QTAB_N
+    F29* apw29 = reinterpret_cast<F29*>(rp_lds + 3 * F29_QTAB_N);
+    f29_qtab_init(qt);
+    // the alpha powers' LDS copy: the launch sized it for wp entries after the table
+    // (wave-uniform, so every lane reaches the barrier or none does)
+    const bool fits = LSP_BOUNDS(3 * F29_QTAB_N * sizeof(uint4) + (size_t)a.wp * sizeof(F29) <= a.lds_max);
+    if (fits)
+        for (uint32_t k = threadIdx.x; k < a.wp; k += blockDim.x) apw29[k] = f29_from_fr(a.apw[k]);
+    __syncthreads();
+    const size_t i = gtid();
+    if (i >= a.n || !fits) return;
+    const Fr* row = a.prep + i * a.wp;
+    constexpr uint32_t RC = RR_CHUNK;
+    auto load = [&](uint32_t k, Fr* dst) {
+#pragma unroll
+        for (uint32_t j = 0; j < RC; ++j)
+            if (k + j < a.wp) dst[j] = row[k + j];
+    };
+    const Fr zi = a.inv_z[i], zni = a.inv_zn[i], old = a.out[i];
+    Fr cur[RC], nxt[RC];
+    load(0, cur);
+    F29 rr = f29_zero();
+    for (uint32_t k = 0; k < a.wp; k += RC) {
+        if (k + RC < a.wp) load(k + RC, nxt);
+        F29 s = rr;
+#pragma unroll
+        for (uint32_t j = 0; j < RC; ++j)
+            if (k + j < a.wp) s = f29_lazy2(s, f29_mul(f29_repack_in(cur[j]), apw29[k + j]));  // < 8.06 r each
+        rr = f29_reduce_qt(s, qt);  // < 2 r
+        if (k + RC < a.wp) {
+#pragma unroll
+            for (uint32_t j = 0; j < RC; ++j) cur[j] = nxt[j];
+        }
+    }
+    const F29 t1 = f29_mul(f29_mul(f29_sub16(f29_repack_in(a.ry_z), rr), f29_from_fr(zi)), f29_from_fr(a.off_z));
+    const F29 t2 = f29_mul(f29_mul(f29_sub16(f29_repack_in(a.ry_zn), rr), f29_from_fr(zni)), f29_from_fr(a.off_zn));
+    a.out[i] = fr_reduce_once(f29_repack_out(f29_reduce_qt(f29_lazy3(t1, t2, f29_repack_in(old)), qt)));
+}
+
 // coef[0..npts) = alpha offsets, coef[npts..2 npts) = offset * reduced ys; apw = alpha^c, c < w
 __global__ __launch_bounds__(256) void k_reduce_matrix(const Fr* __restrict__ M, size_t n, uint32_t w,
                                                        const Fr* __restrict__ apw, uint32_t npts,
@@ -258,6 +307,23 @@ hipError_t launch_reduce_rows(const ReduceArgs& a, hipStream_t st) {
     if (!a.consts29) return hipErrorInvalidValue;  // the caller must pass the global scratch (reduce_rows_scratch)
     hipLaunchKernelGGL(k_reduce_consts, dim3(nblocks(nconst, 256)), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_reduce_rows<true>, dim3(nblocks(a.n, 256)), dim3(256), qtab, st, a);
+    return hipGetLastError();
+}
+
+bool reduce_prep_fits(uint32_t wp, size_t lds_max) {
+    return 3 * F29_QTAB_N * sizeof(uint4) + (size_t)wp * sizeof(F29) <= lds_max;
+}
+
+hipError_t launch_reduce_prep(const PrepReduceArgs& a, hipStream_t st) {
+    if (!a.prep || !a.wp || !a.inv_z || !a.inv_zn || !a.apw || !a.out || !reduce_prep_fits(a.wp, a.lds_max))
+        return hipErrorInvalidValue;
+    const size_t lds = 3 * F29_QTAB_N * sizeof(uint4) + (size_t)a.wp * sizeof(F29);
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_reduce_prep),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_reduce_prep, dim3(nblocks(a.n, 256)), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 

@@ -171,7 +171,12 @@ __global__ __launch_bounds__(256) void k_quotient(QuotientArgs a) {
             PUSH(F.mul(last, lchk));
         } else if constexpr (PROG) {  // LSP_AIR_PROGRAM: the selectors are operands, an assert's value is pushed as it stands
             extern __shared__ uint32_t prog_regs[];
-            const ProgEnv e{loc, nxt, a.w, a.pub, a.npub, first, last, trans, prog_regs, a.prog_slots};
+            // the preprocessed matrix at the rows of `loc` and `nxt`
+            const ProgEnv e{loc,        nxt,          a.w,
+                            a.pub,      a.npub,       first,
+                            last,       trans,        prog_regs,
+                            a.prog_slots, a.prep + lrow * a.wp, a.prep + nrow * a.wp,
+                            a.wp};
             p = air_prog_run(F, e, d, p, [&](const F29& v) { PUSH(v); });
         }
     }
@@ -233,6 +238,8 @@ static QuotientArgs with_order(const QuotientArgs& a) {
 template <bool EARLY>
 static hipError_t launch_quotient_prog_t(const QuotientArgs& b, size_t n, hipStream_t st) {
     if (!b.pub || b.npub < 2 || b.prog_slots > 16) return hipErrorInvalidValue;
+    // a preprocessed matrix is the whole LDE, indexed like `lde` from row 0
+    if (b.wp && (!b.prep || b.row0 || b.lde_next)) return hipErrorInvalidValue;
     const uint32_t bs = air_prog_block(b.prog_slots);
     const size_t lds = air_prog_lds_bytes(b.prog_slots, bs);
     if (lds > 48 * 1024) {

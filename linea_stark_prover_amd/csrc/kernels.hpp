@@ -229,6 +229,12 @@ struct QuotientArgs {
     const Fr* pub = nullptr;
     uint32_t npub = 0;
     uint32_t prog = 0, prog_slots = 0;
+    // LSP_AIR_PROGRAM_PREP configs: the LDE of the preprocessed matrix, N x wp
+    // in the layout of `lde`, read at the same two rows (the whole LDE:
+    // row0 = 0, no lde_next).  Read only by the program-capable walker; last in
+    // the struct, so the built-in walker's arguments stay where they were.
+    const Fr* prep = nullptr;
+    uint32_t wp = 0;
 };
 // den[m] = (x_i - 1)(x_i - w_h^-1), x_i = GEN * w_Q^i, i = i0 + (m << log_step), m < n
 hipError_t launch_selector_denoms(const Fr* tabQ, uint32_t L1, Fr gen, Fr wh_inv, size_t n, Fr* den,
@@ -263,6 +269,10 @@ struct CheckArgs {
     const Fr* pub = nullptr;
     uint32_t npub = 0;
     uint32_t prog = 0, prog_slots = 0;
+    // LSP_AIR_PROGRAM_PREP configs: the preprocessed matrix itself, h x wp
+    // row-major in natural order, read at the rows of `trace`
+    const Fr* prep = nullptr;
+    uint32_t wp = 0;
 };
 hipError_t launch_check(const CheckArgs& a, hipStream_t st);
 hipError_t launch_check_rows(const CheckArgs& a, hipStream_t st);
@@ -306,6 +316,27 @@ inline size_t reduce_rows_scratch(uint32_t w, uint32_t q, size_t lds_max) {
     return lds <= lds_max ? 0 : w + 1 + 2 * (size_t)q;
 }
 hipError_t launch_reduce_rows(const ReduceArgs& a, hipStream_t st);
+// The preprocessed matrix as a third matrix at two points, accumulated into the
+// FRI input launch_reduce_rows wrote (proofs with a preprocessed matrix only):
+//   out[i] += off_z (ry_z - rr_i) inv_z[i] + off_zn (ry_zn - rr_i) inv_zn[i],
+//   rr_i = sum_c apw[c] prep[i][c], c < wp
+// with off_z = alpha_fri^(2w+q), off_zn = alpha_fri^(2w+q+wp) continuing the
+// running power and ry_* the opened values reduced by apw.  One pass over the
+// N x wp matrix on the 29-bit product, the alpha powers in the workgroup's LDS.
+struct PrepReduceArgs {
+    const Fr* prep;  // N x wp
+    uint32_t wp;
+    const Fr* inv_z;
+    const Fr* inv_zn;
+    const Fr* apw;  // alpha_fri^c, c < wp (device)
+    Fr ry_z, ry_zn, off_z, off_zn;
+    Fr* out;  // N, read and written
+    size_t n;
+    size_t lds_max = 64 * 1024;
+};
+// whether wp alpha powers fit the workgroup's LDS beside the reduction table (about 4,400 columns on gfx950)
+bool reduce_prep_fits(uint32_t wp, size_t lds_max);
+hipError_t launch_reduce_prep(const PrepReduceArgs& a, hipStream_t st);
 // one deliberately failing LSP_BOUNDS check (dbg_bounds.hpp; a no-op kernel in the product build)
 hipError_t launch_bounds_probe(uint32_t* sink, hipStream_t st);
 #ifdef LSP_DEBUG_BOUNDS

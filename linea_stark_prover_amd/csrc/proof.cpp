@@ -141,7 +141,14 @@ std::vector<lsp_query> recycled_queries() {
 }
 
 std::vector<uint8_t> serialize(const lsp_proof& p, HostPool* pool, std::vector<uint8_t>* reuse) {
+    // with a preprocessed matrix (p.wp > 0) the format is LSPPRF03: prep_width after
+    // final_poly_len, the two opened rows after the chunks', a third opening per query
+    const bool prep = p.wp != 0;
     size_t nfr = 3 + p.tl.size() + p.tn.size() + p.qc.size() + p.roots.size() + p.final_poly.size(), nu32 = 6;
+    if (prep) {
+        nfr += p.pl.size() + p.pn.size();
+        nu32 += 1;
+    }
     // byte offset of every query's record (queries are written independently)
     std::vector<size_t> qoff(p.queries.size() + 1);
     size_t qbytes = 0;
@@ -149,6 +156,10 @@ std::vector<uint8_t> serialize(const lsp_proof& p, HostPool* pool, std::vector<u
         const auto& q = p.queries[i];
         size_t f = q.trow.size() + q.tpath.size() + q.qrow.size() + q.qpath.size() + q.sib.size(), u = 2 + q.sib.size();
         for (auto& fp : q.fpath) f += fp.size();
+        if (prep) {
+            f += q.prow.size() + q.ppath.size();
+            u += 1;
+        }
         qoff[i] = qbytes;
         qbytes += 32 * f + 4 * u;
     }
@@ -158,7 +169,7 @@ std::vector<uint8_t> serialize(const lsp_proof& p, HostPool* pool, std::vector<u
     // every byte is written below, so a recycled buffer needs no clearing
     // (resize value-initialises only what it adds)
     b.resize(head + qbytes);
-    std::memcpy(b.data(), "LSPPRF02", 8);
+    std::memcpy(b.data(), prep ? "LSPPRF03" : "LSPPRF02", 8);
     Writer w{b.data() + 8};
     w.u32(p.log_h);
     w.u32(p.log_q);
@@ -166,11 +177,16 @@ std::vector<uint8_t> serialize(const lsp_proof& p, HostPool* pool, std::vector<u
     w.u32((uint32_t)p.queries.size());
     w.u32((uint32_t)p.roots.size());
     w.u32((uint32_t)p.final_poly.size());
+    if (prep) w.u32(p.wp);
     w.fr(p.troot);
     w.fr(p.qroot);
     w.frs(p.tl);
     w.frs(p.tn);
     w.frs(p.qc);
+    if (prep) {
+        w.frs(p.pl);
+        w.frs(p.pn);
+    }
     w.frs(p.roots);
     w.frs(p.final_poly);
     w.fr(p.pow_w);
@@ -184,6 +200,11 @@ std::vector<uint8_t> serialize(const lsp_proof& p, HostPool* pool, std::vector<u
         wq.frs(q.qrow);
         wq.u32((uint32_t)q.qpath.size());
         wq.frs(q.qpath);
+        if (prep) {
+            wq.frs(q.prow);
+            wq.u32((uint32_t)q.ppath.size());
+            wq.frs(q.ppath);
+        }
         for (size_t r = 0; r < q.sib.size(); ++r) {
             wq.fr(q.sib[r]);
             wq.u32((uint32_t)q.fpath[r].size());
@@ -200,8 +221,9 @@ std::vector<uint8_t> serialize(const lsp_proof& p, HostPool* pool, std::vector<u
 // Untrusted bytes: every count is range-checked before anything is sized by
 // it, and the buffer must be consumed exactly.
 lsp_proof* deserialize(const uint8_t* buf, size_t len) {
-    if (!buf || len < 8 + 24 || std::memcmp(buf, "LSPPRF02", 8) != 0)
-        throw LspError(LSP_E_ARG, "not an LSPPRF02 proof");
+    const bool prep = buf && len >= 8 && std::memcmp(buf, "LSPPRF03", 8) == 0;
+    if (!buf || len < 8 + 24 || (!prep && std::memcmp(buf, "LSPPRF02", 8) != 0))
+        throw LspError(LSP_E_ARG, "not an LSPPRF02 or LSPPRF03 proof");
     Reader r{buf, len};
     r.off = 8;
     auto p = std::make_unique<lsp_proof>();
@@ -209,6 +231,10 @@ lsp_proof* deserialize(const uint8_t* buf, size_t len) {
     p->log_q = r.u32();
     p->w = r.u32();
     const uint32_t nq = r.u32(), nr = r.u32(), nf = r.u32();
+    // LSPPRF03: the preprocessed matrix's width, range-checked like the trace's
+    // before anything is sized by it (Reader::frs refuses what the bytes cannot hold)
+    p->wp = prep ? r.u32() : 0;
+    if (prep && (r.bad || p->wp == 0 || p->wp > (1u << 20))) throw LspError(LSP_E_ARG, "proof header out of range");
     if (r.bad || p->log_h > 40 || p->log_q > 20 || p->w == 0 || p->w > (1u << 20) || nr > 64 || nq > (1u << 20) ||
         nf == 0 || nf > (1u << 20) || (nf & (nf - 1)) != 0)
         throw LspError(LSP_E_ARG, "proof header out of range");
@@ -218,16 +244,24 @@ lsp_proof* deserialize(const uint8_t* buf, size_t len) {
     r.frs(p->tl, p->w);
     r.frs(p->tn, p->w);
     r.frs(p->qc, q);
+    if (prep) {
+        r.frs(p->pl, p->wp);
+        r.frs(p->pn, p->wp);
+    }
     r.frs(p->roots, nr);
     r.frs(p->final_poly, nf);
     p->pow_w = r.fr();
-    if (r.bad || nq > (len - r.off) / (32 * (p->w + q))) throw LspError(LSP_E_ARG, "malformed proof bytes");
+    if (r.bad || nq > (len - r.off) / (32 * (p->w + q + p->wp))) throw LspError(LSP_E_ARG, "malformed proof bytes");
     p->queries.resize(nq);
     for (auto& qq : p->queries) {
         r.frs(qq.trow, p->w);
         r.frs(qq.tpath, r.u32());
         r.frs(qq.qrow, q);
         r.frs(qq.qpath, r.u32());
+        if (prep) {
+            r.frs(qq.prow, p->wp);
+            r.frs(qq.ppath, r.u32());
+        }
         qq.sib.resize(nr);
         qq.fpath.resize(nr);
         for (uint32_t k = 0; k < nr && !r.bad; ++k) {
@@ -248,7 +282,38 @@ struct Flat {
     std::vector<uint32_t> fri_path_lens;
     uint32_t input_path_len = 0;
 };
+// the same for lsp_proof_preprocessed_view (a cache of its own inside the proof's)
+struct PrepFlat {
+    std::vector<Fr> rows, paths;
+    uint32_t path_len = 0;
+};
 }  // namespace
+
+void proof_prep_view(const lsp_proof& p, lsp_proof_preprocessed_view* v) {
+    LSP_REQUIRE(p.wp != 0, LSP_E_STATE, "an LSPPRF02 proof has no preprocessed openings");
+    std::lock_guard<std::mutex> g(p.cache_mu);
+    if (!p.prep_view_cache) {
+        auto f = std::make_shared<PrepFlat>();
+        f->path_len = p.queries.empty() ? 0 : (uint32_t)p.queries[0].ppath.size();
+        LSP_REQUIRE(p.pl.size() == p.wp && p.pn.size() == p.wp, LSP_E_STATE, "preprocessed opened values missing");
+        for (auto& q : p.queries) {
+            if (q.prow.size() != p.wp || q.ppath.size() != f->path_len)
+                throw LspError(LSP_E_STATE, "proof queries are not uniform");
+            f->rows.insert(f->rows.end(), q.prow.begin(), q.prow.end());
+            f->paths.insert(f->paths.end(), q.ppath.begin(), q.ppath.end());
+        }
+        p.prep_view_cache = f;
+    }
+    const PrepFlat& f = *std::static_pointer_cast<PrepFlat>(p.prep_view_cache);
+    auto fr = [](const std::vector<Fr>& x) { return reinterpret_cast<const lsp_fr*>(x.data()); };
+    std::memset(v, 0, sizeof *v);
+    v->width = p.wp;
+    v->local = fr(p.pl);
+    v->next = fr(p.pn);
+    v->rows = fr(f.rows);
+    v->paths = fr(f.paths);
+    v->path_len = f.path_len;
+}
 
 void proof_view(const lsp_proof& p, lsp_proof_view* v) {
     // built once, under the proof's cache mutex; never replaced afterwards, so

@@ -184,8 +184,9 @@ struct Shard {
     uint32_t logGq;
 };
 
-Shard shard_geometry(const lsp_ctx* ctx, const Comm& comm, size_t h, size_t w, const Air& air, size_t npub) {
-    air.require_fits(w, npub);
+Shard shard_geometry(const lsp_ctx* ctx, const Comm& comm, size_t h, size_t w, const Air& air, size_t npub,
+                     size_t wp = 0) {
+    air.require_fits(w, npub, wp);
     Shard s;
     s.h = h;
     s.w = w;
@@ -263,6 +264,11 @@ struct Prover {
     bool early = false, side_pending = false;
     std::function<void(hipEvent_t)> side_fn;
     Fr *inv_z = nullptr, *inv_zn = nullptr;  // 1 / (zeta - x), 1 / (zeta w_h - x) over this rank's rows
+    // the preprocessed matrix (one rank only): the tree's LDE and layers, all on
+    // the device, and its width (0: the proof has none)
+    const Fr *plde = nullptr, *play = nullptr;
+    size_t wp = 0;
+    Fr proot;
     // FRI: this rank's slice of round r's input (length (N >> r) / G), back to
     // back in fvec; the commit phase's cursor (fv + vo: the current round's
     // input of global length len, ftree + to: its tree) and the fold it owes
@@ -396,6 +402,10 @@ struct Prover {
         qa.row0_next = row0_next;
         qa.lde_rows = S;
         qa.lde_next_rows = lde_next ? S : 0;
+        if (wp && air.has_prog) {  // the same lrow / nrow of the preprocessed LDE
+            qa.prep = plde;
+            qa.wp = (uint32_t)wp;
+        }
     }
 
     // Constraints before alpha (round 4): every constraint C_j at this rank's
@@ -504,24 +514,26 @@ struct Prover {
         // that evaluated no quotient points (g >= Gq), each over its first coset,
         // instead of all to rank 0; an allgather of the values replaces rank 0's
         // broadcast.  sub: the low coset's h / S ranks add partial sums.
-        const size_t maxw = std::max(w, q);
-        const size_t nsum = 2 * w + q;
+        // (with a preprocessed matrix: two more jobs, the matrix at zeta and at zeta*w_h)
+        const int nj = wp ? 5 : 3;
+        const size_t maxw = std::max({w, q, wp});
+        const size_t nsum = 2 * w + q + 2 * wp;
         Fr* sums = ctx->fbuf("o_sums", nsum);
         const size_t nlow = std::min(S, h);  // this rank's rows of one coset
-        const size_t joff[3] = {0, w, 2 * w}, jw[3] = {w, w, q};
-        bool job_here[3] = {false, false, false};
+        const size_t joff[5] = {0, w, 2 * w, 2 * w + q, 2 * w + q + wp}, jw[5] = {w, w, q, wp, wp};
+        bool job_here[5] = {false, false, false, false, false};
         if (s.sub) {
             job_here[0] = job_here[1] = job_here[2] = row0 < h;  // ranks 0 .. h/S - 1: the low coset's partial sums
         } else {
             const uint32_t nfree = G > s.Gq ? (uint32_t)(G - s.Gq) : 0u;
-            for (int j = 0; j < 3; ++j)
+            for (int j = 0; j < nj; ++j)
                 job_here[j] = g == (nfree ? G - 1 - (uint32_t)j % nfree : G - 1 - (uint32_t)j % G);
         }
         if (job_here[0] || job_here[1] || job_here[2]) {
             ctx->fbuf("o_partial", ((nlow + 1023) / 1024) * maxw);  // the drivers' scratch, sized once for the widest job
-            const Fr* jm[3] = {lde, lde, qlde};
-            const Fr* jinv[3] = {inv_z, inv_zn, inv_z};
-            for (int j = 0; j < 3; ++j)
+            const Fr* jm[5] = {lde, lde, qlde, plde, plde};
+            const Fr* jinv[5] = {inv_z, inv_zn, inv_z, inv_z, inv_zn};
+            for (int j = 0; j < nj; ++j)
                 if (job_here[j])
                     barycentric_sums(ctx, jm[j], (uint32_t)jw[j], nlow, jinv[j], GEN, logN, row0, sums + joff[j]);
         }
@@ -533,8 +545,8 @@ struct Prover {
         // the coset of this rank's first rows: c = GEN w_N^bitrev(row0) (sub: the low coset, GEN)
         const Fr cpos = s.sub ? GEN : fr_mul(GEN, fr_pow_u64(host_two_adic_generator(logN), host_bitrev(row0, logN)));
         const CosetFactor factor(cpos, h, true);
-        const Fr jz[3] = {zeta, zeta_next, zeta};
-        for (int j = 0; j < 3; ++j) {
+        const Fr jz[5] = {zeta, zeta_next, zeta, zeta, zeta_next};
+        for (int j = 0; j < nj; ++j) {
             const Fr f = factor.at(jz[j]);
             for (size_t k = 0; k < jw[j]; ++k) hs[joff[j] + k] = job_here[j] ? fr_mul(hs[joff[j] + k], f) : fr_zero();
         }
@@ -549,6 +561,10 @@ struct Prover {
         proof->tl.assign(hs, hs + w);
         proof->tn.assign(hs + w, hs + 2 * w);
         proof->qc.assign(hs + 2 * w, hs + 2 * w + q);
+        if (wp) {
+            proof->pl.assign(hs + joff[3], hs + joff[3] + wp);
+            proof->pn.assign(hs + joff[4], hs + joff[4] + wp);
+        }
         T.end("compute opened values with Lagrange interpolation");
     }
 
@@ -615,7 +631,32 @@ struct Prover {
         if (const size_t nsc = reduce_rows_scratch(ra.w, ra.q, ra.lds_max))  // constants beyond the LDS: global
             ra.consts29 = (F29*)ctx->buf("o_rr_consts", nsc * sizeof(F29));
         LSP_HIP(launch_reduce_rows(ra, st));
+        if (wp) reduce_prep(alpha_fri, 2 * w + q);
         T.end("reduce rows");
+    }
+
+    // the preprocessed matrix as a third matrix at zeta and zeta*w_h, continuing
+    // the running power from alpha_fri^done: accumulated into fvec
+    void reduce_prep(const Fr& alpha_fri, size_t done) {
+        span("reduce matrix preprocessed at zeta", wp, s.N, -1);
+        span("reduce matrix preprocessed at zeta*w", wp, s.N, -1);
+        const std::vector<Fr> apw = alpha_powers(alpha_fri, wp);
+        Fr* dapw = ctx->fbuf("o_apw_prep", wp);
+        ctx->h2d_async("o_apw_prep_h", dapw, apw.data(), wp * sizeof(Fr));
+        PrepReduceArgs pa;
+        pa.prep = plde;
+        pa.wp = (uint32_t)wp;
+        pa.inv_z = inv_z;
+        pa.inv_zn = inv_zn;
+        pa.apw = dapw;
+        pa.ry_z = reduce_opened(apw.data(), proof->pl.data(), wp);
+        pa.ry_zn = reduce_opened(apw.data(), proof->pn.data(), wp);
+        pa.off_z = fr_pow_u64(alpha_fri, done);
+        pa.off_zn = fr_pow_u64(alpha_fri, done + wp);
+        pa.out = fvec;
+        pa.n = s.S;
+        pa.lds_max = ctx->lds_per_block;
+        LSP_HIP(launch_reduce_prep(pa, st));
     }
 
     // ---- FRI commit phase: per round the tree of the vector's pairs, its root
@@ -833,6 +874,7 @@ struct Prover {
         q1 = host_clock::now();
         const uint32_t nq = (uint32_t)idxs.size();
         size_t E = s.w + s.logS + s.q + s.logS;  // elements per query below the rank subtrees
+        if (wp) E += wp + s.logS;                // the preprocessed row and its whole path (one rank: logS = logN)
         for (const FriRound& R : rounds) E += 1 + log2_exact(R.ml);
         std::vector<uint64_t> ptrs;
         std::vector<uint32_t> mine;
@@ -885,6 +927,10 @@ struct Prover {
             path(tlay, S, li);
             for (size_t j = 0; j < q; ++j) P(qlde + li * q + j);
             path(qlay, S, li);
+            if (wp) {  // (one rank: li = idx, S = N, the tree's layers hold every level)
+                for (size_t c = 0; c < wp; ++c) P(plde + li * wp + c);
+                path(play, S, li);
+            }
             for (size_t r = 0; r < rounds.size(); ++r) {
                 const FriRound& R = rounds[r];
                 const size_t ii = idx >> r;                                  // global index in round r's vector
@@ -950,6 +996,12 @@ struct Prover {
             qq.qpath.assign(e, e + logS);
             e += logS;
             top_path(qtop, o, qq.qpath);
+            if (wp) {
+                qq.prow.assign(e, e + wp);
+                e += wp;
+                qq.ppath.assign(e, e + logS);
+                e += logS;
+            }
             for (uint32_t r = 0; r < nr; ++r) {
                 const FriRound& R = rounds[r];
                 qq.sib.push_back(*e++);
@@ -983,13 +1035,29 @@ struct Prover {
 }  // namespace
 
 lsp_proof* prove_shard(lsp_ctx* ctx, Comm& comm, const Fr* d_trace, size_t h, size_t w, const Air& air,
-                       const Fr* pub, size_t npub) {
+                       const Fr* pub, size_t npub, const lsp_tree* prep) {
     const auto t_entry = host_clock::now();
     const ActiveProof active;
     const DeferTopUploads defer(ctx);
     comm.begin_log(ctx);
-    const Shard geo = shard_geometry(ctx, comm, h, w, air, npub);
+    const size_t wp = prep && !prep->widths.empty() ? prep->widths[0] : 0;
+    const Shard geo = shard_geometry(ctx, comm, h, w, air, npub, wp);
     Prover P(ctx, comm, d_trace, air, pub, npub, geo, t_entry);
+    if (prep) {
+        LSP_REQUIRE(geo.G == 1, LSP_E_ARG, "a preprocessed matrix is proved on one rank only");
+        // the tree's own context: its layers went up on this stream (a commit's host-made
+        // top is uploaded asynchronously) and this call holds the mutex that guards them
+        LSP_REQUIRE(prep->ctx == ctx, LSP_E_ARG, "the preprocessed tree belongs to another context");
+        LSP_REQUIRE(prep->height == geo.N && prep->mats.size() == 1 && wp >= 1, LSP_E_ARG,
+                    "the preprocessed tree is not over one matrix of height h << log_blowup");
+        LSP_REQUIRE(reduce_prep_fits((uint32_t)wp, ctx->lds_per_block), LSP_E_ARG,
+                    "the preprocessed matrix is wider than the reduce kernel's LDS holds");
+        P.plde = prep->mats[0];
+        P.play = prep->layers;
+        P.wp = wp;
+        P.proof->wp = (uint32_t)wp;
+        P.proot = d2h_fr(ctx, prep->layers + 2 * geo.N - 2);  // the root: the last of the 2N - 1 digests
+    }
 
     P.commit_trace();
     // U7: the instance, then the quotient challenge (TranscriptCfg switches)
@@ -997,6 +1065,7 @@ lsp_proof* prove_shard(lsp_ctx* ctx, Comm& comm, const Fr* d_trace, size_t h, si
     Challenger ch(&ctx->p2, TC.mont_bits);
     if (TC.log_degree) ch.observe(fr_from_u64(geo.log_h));
     ch.observe(P.proof->troot);
+    if (prep) ch.observe(P.proot);  // U13
     if (TC.public_values)
         for (size_t i = 0; i < npub; ++i) ch.observe(pub[i]);
     const Fr alpha = ch.sample();
@@ -1014,6 +1083,8 @@ lsp_proof* prove_shard(lsp_ctx* ctx, Comm& comm, const Fr* d_trace, size_t h, si
         for (const Fr& v : P.proof->tl) ch.observe(v);
         for (const Fr& v : P.proof->tn) ch.observe(v);
         for (const Fr& v : P.proof->qc) ch.observe(v);
+        for (const Fr& v : P.proof->pl) ch.observe(v);
+        for (const Fr& v : P.proof->pn) ch.observe(v);
     }
     const Fr alpha_fri = ch.sample();
 
@@ -1034,9 +1105,9 @@ lsp_proof* prove_shard(lsp_ctx* ctx, Comm& comm, const Fr* d_trace, size_t h, si
 }
 
 lsp_proof* prove_device(lsp_ctx* ctx, const Fr* d_trace, size_t h, size_t w, const Air& air, const Fr* pub,
-                        size_t npub) {
+                        size_t npub, const lsp_tree* prep) {
     SoloComm solo;
-    return prove_shard(ctx, solo, d_trace, h, w, air, pub, npub);
+    return prove_shard(ctx, solo, d_trace, h, w, air, pub, npub, prep);
 }
 
 }  // namespace lsp

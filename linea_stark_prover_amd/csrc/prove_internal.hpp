@@ -99,26 +99,31 @@ void resolve_timings(lsp_ctx* ctx);
 // and the host's tree top
 Fr commit_device(lsp_ctx* ctx, const MatList& m, size_t height, Fr* layers, const FoldSpec* fold = nullptr,
                  const std::function<void(hipEvent_t)>* side = nullptr);
+// prep (optional): the committed preprocessed matrix -- a tree of ctx itself over
+// exactly one matrix of height h << log_blowup (lsp_preprocess's, or an
+// lsp_merkle_commit over a caller-made LDE); the proof then opens it too (LSPPRF03)
 lsp_proof* prove_device(lsp_ctx* ctx, const Fr* d_trace, size_t h, size_t w, const Air& air, const Fr* pub,
-                        size_t npub);
+                        size_t npub, const lsp_tree* prep = nullptr);
 // p3-uni-stark check_constraints over the h x w trace (check.cpp): the device
 // path (k_check.hip; d_trace on ctx's GPU) and the host loop fill the same
-// report; list = the first `cap` violations in (row, constraint) order
+// report; list = the first `cap` violations in (row, constraint) order.
+// prep (optional): the raw h x wp preprocessed matrix, where the trace is
 struct CheckReport {
     lsp_check_summary s;
     std::vector<uint64_t> counts, first_rows;  // per constraint; first_rows UINT64_MAX = none
     std::vector<lsp_violation> list;
 };
 CheckReport check_constraints_device(lsp_ctx* ctx, const Fr* d_trace, size_t h, size_t w, const Air& air,
-                                     const Fr* pub, size_t npub, size_t cap);
+                                     const Fr* pub, size_t npub, size_t cap, const Fr* d_prep = nullptr,
+                                     size_t wp = 0);
 CheckReport check_constraints_host(const Fr* trace, size_t h, size_t w, const Air& air, const Fr* pub, size_t npub,
-                                   size_t cap);
+                                   size_t cap, const Fr* prep = nullptr, size_t wp = 0);
 // "constraints had nonzero value on row R: constraint J (config C, <kind>[, table T]); N rows fail"
 std::string check_failure_message(const Air& air, const CheckReport& r);
 // one rank of a proof sharded over comm.size ranks (prove_device = 1 rank);
 // every rank returns the same proof
 lsp_proof* prove_shard(lsp_ctx* ctx, Comm& comm, const Fr* d_trace, size_t h, size_t w, const Air& air,
-                       const Fr* pub, size_t npub);
+                       const Fr* pub, size_t npub, const lsp_tree* prep = nullptr);
 // collective (every rank of comm): time an allgather of up to 256 MiB and this
 // GPU's inverse NTT, agree on the minimum over the ranks (comm.ag_gbs,
 // comm.intt_gelem_s; every rank's raw values in comm.calib_raw)
@@ -159,6 +164,8 @@ void proof_release(lsp_proof* p);
 std::vector<uint8_t> recycled_wire();
 std::vector<lsp_query> recycled_queries();
 void proof_view(const lsp_proof& p, lsp_proof_view* v);
+// the preprocessed openings of an LSPPRF03 proof; LSP_E_STATE on an LSPPRF02 one
+void proof_prep_view(const lsp_proof& p, lsp_proof_preprocessed_view* v);
 lsp_proof* proof_from_view(const lsp_proof_view& v);
 // communicators of a process-per-GPU sharded prove (comm_ext.cpp)
 Comm* make_callback_comm(const lsp_comm_ops& ops);
@@ -174,6 +181,9 @@ void witness_lookup_device(lsp_ctx* ctx, const Fr* a, uint32_t na, const Fr* b, 
 lsp_raw_trace* parse_raw_trace(const uint8_t* buf, size_t len);
 void raw_trace_shape(const lsp_raw_trace& t, size_t& height, size_t& width);
 std::vector<Fr> raw_trace_columns(const lsp_raw_trace& t, size_t height);
-// 0 = accept, otherwise the failing check (host CPU verifier)
-int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, const uint8_t* b, size_t n);
+// 0 = accept, otherwise the failing check (host CPU verifier).  prep_commit
+// (optional) and prep_width: the preprocessed matrix's root and width, for an
+// "LSPPRF03" proof (verify.cpp)
+int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, const uint8_t* b, size_t n,
+                const Fr* prep_commit = nullptr, uint32_t prep_width = 0);
 }  // namespace lsp

@@ -55,12 +55,24 @@ bool mk_verify(const P2Host& p2, const Fr& root, size_t index, const Fr* leaf, s
 }
 }  // namespace
 
-int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, const uint8_t* b, size_t n) {
+// prep_commit (optional) with prep_width: the verifier's own data about the
+// AIR's preprocessed matrix (p3's VerifierData), never proof fields.  Such a
+// proof is "LSPPRF03": LSPPRF02 with u32 prep_width after final_poly_len,
+// prep@zeta[wp] and prep@zeta*w[wp] after chunks@zeta[q], and per query, after
+// the quotient row and path, the preprocessed row[wp] and u32 len + path.  The
+// root is observed after the trace root (U13), the opened values after the
+// chunks', and the FRI input continues the running alpha_fri power with the
+// matrix at zeta, then at zeta*w.  Each format is rejected where the other is
+// expected.
+int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, const uint8_t* b, size_t n,
+                const Fr* prep_commit, uint32_t prep_width) {
     if (npub < 2) return 1;
-    if (n < 8 || std::memcmp(b, "LSPPRF02", 8) != 0) return 2;
+    if (n < 8 || std::memcmp(b, prep_commit ? "LSPPRF03" : "LSPPRF02", 8) != 0) return 2;
     Reader r{b, n};
     r.off = 8;
     const uint32_t log_h = r.u32(), log_q = r.u32(), w = r.u32(), nq = r.u32(), nr = r.u32(), nf = r.u32();
+    const uint32_t wp = prep_commit ? r.u32() : 0;
+    if (wp != prep_width || wp > (1u << 20) || air.prep_width > wp || (prep_commit && wp == 0)) return 3;
     if (r.bad || log_q != air.log_quotient_degree(ctx->public_degree) || nq != ctx->num_queries || log_h > 40 ||
         log_h < 1 || w <= air.max_col || w > (1u << 20) || air.max_pub >= (int64_t)npub)
         return 3;
@@ -69,10 +81,13 @@ int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, 
     const size_t q = (size_t)1 << log_q, h = (size_t)1 << log_h;
     const size_t flen = (size_t)1 << ctx->log_final_poly_len;
     const Fr troot = r.fr(), qroot = r.fr();
-    std::vector<Fr> tl(w), tn(w), qc(q), roots(nr), betas(nr), fp(flen);
+    if (r.n - r.off < ((size_t)2 * w + q + 2 * (size_t)wp) * 32) return 5;  // (before any allocation by a claimed width)
+    std::vector<Fr> tl(w), tn(w), qc(q), pl(wp), pn(wp), roots(nr), betas(nr), fp(flen);
     for (auto& x : tl) x = r.fr();
     for (auto& x : tn) x = r.fr();
     for (auto& x : qc) x = r.fr();
+    for (auto& x : pl) x = r.fr();
+    for (auto& x : pn) x = r.fr();
     for (auto& x : roots) x = r.fr();
     for (auto& x : fp) x = r.fr();
     const Fr pw = r.fr();
@@ -82,6 +97,7 @@ int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, 
     Challenger ch(&ctx->p2, TC.mont_bits);
     if (TC.log_degree) ch.observe(fr_from_u64(log_h));
     ch.observe(troot);
+    if (prep_commit) ch.observe(*prep_commit);  // U13
     if (TC.public_values)
         for (size_t i = 0; i < npub; ++i) ch.observe(pub[i]);
     const Fr alpha = ch.sample();
@@ -93,6 +109,8 @@ int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, 
         for (const Fr& v : tl) ch.observe(v);
         for (const Fr& v : tn) ch.observe(v);
         for (const Fr& v : qc) ch.observe(v);
+        for (const Fr& v : pl) ch.observe(v);
+        for (const Fr& v : pn) ch.observe(v);
     }
     const Fr alpha_fri = ch.sample();
     for (uint32_t k = 0; k < nr; ++k) {
@@ -106,13 +124,17 @@ int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, 
         if (pwc.v[i]) return 6;
     if (!ch.check_witness(ctx->pow_bits, (uint64_t)pwc.v[0] | ((uint64_t)pwc.v[1] << 32))) return 7;
     const Fr gN = host_two_adic_generator(logN);
-    std::vector<Fr> trow(w), qrow(q);
+    std::vector<Fr> trow(w), qrow(q), prow(wp);
     for (uint32_t qi = 0; qi < nq; ++qi) {
         const size_t idx = (size_t)ch.sample_bits(logN);
         for (auto& x : trow) x = r.fr();
         if (!mk_verify(ctx->p2, troot, idx, trow.data(), w, r, logN)) return 8;
         for (auto& x : qrow) x = r.fr();
         if (!mk_verify(ctx->p2, qroot, idx, qrow.data(), q, r, logN)) return 9;
+        if (prep_commit) {
+            for (auto& x : prow) x = r.fr();
+            if (!mk_verify(ctx->p2, *prep_commit, idx, prow.data(), wp, r, logN)) return 14;
+        }
         const Fr x = fr_mul(GEN, fr_pow_u64(gN, host_bitrev(idx, logN)));
         const Fr dz = fr_inv(fr_sub(x, zeta)), dzn = fr_inv(fr_sub(x, zeta_next));
         Fr ro = fr_zero(), apow = one;
@@ -126,6 +148,14 @@ int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, 
         }
         for (size_t j = 0; j < q; ++j) {
             ro = fr_add(ro, fr_mul(apow, fr_mul(fr_sub(qrow[j], qc[j]), dz)));
+            apow = fr_mul(apow, alpha_fri);
+        }
+        for (uint32_t c = 0; c < wp; ++c) {
+            ro = fr_add(ro, fr_mul(apow, fr_mul(fr_sub(prow[c], pl[c]), dz)));
+            apow = fr_mul(apow, alpha_fri);
+        }
+        for (uint32_t c = 0; c < wp; ++c) {
+            ro = fr_add(ro, fr_mul(apow, fr_mul(fr_sub(prow[c], pn[c]), dzn)));
             apow = fr_mul(apow, alpha_fri);
         }
         Fr folded = ro;
@@ -168,7 +198,7 @@ int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, 
     const Fr last = fr_mul(zh, fr_inv(fr_sub(zeta, wh_inv)));
     const Fr trans = fr_sub(zeta, wh_inv);
     Fr acc = fr_zero();
-    air.eval_fold(tl.data(), tn.data(), pub, first, last, trans, alpha, acc);
+    air.eval_fold(tl.data(), tn.data(), pub, first, last, trans, alpha, acc, pl.data(), pn.data());
     if (!fr_eq(fr_mul(acc, fr_inv(zh)), quotient)) return 13;
     return 0;
 }

@@ -57,6 +57,27 @@ class LspProofView(ctypes.Structure):
                                               "fri_siblings", "fri_paths")]
 
 
+def preprocessed_openings(h: ctypes.c_void_p) -> dict:
+    """lsp_proof_get_preprocessed_view of a proof handle: the preprocessed matrix's
+    ``width``, its opened values ``local`` / ``next`` (width x 4 each) and per
+    query its ``rows`` (width x 4) and ``paths``.  LspError(LSP_E_STATE) on a
+    proof without a preprocessed matrix (LSPPRF02)."""
+    v = L.LspProofPrepView()
+    L.check(L.lib().lsp_proof_get_preprocessed_view(h, ctypes.byref(v)))
+    pv = LspProofView()
+    L.check(L.lib().lsp_proof_get_view(h, ctypes.byref(pv)))
+
+    def arr(ptr, n):
+        if n == 0:
+            return np.zeros((0, 4), np.uint64)
+        return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_uint64)), (n * 4,)).reshape(n, 4).copy()
+    w, pl, nq = v.width, v.path_len, pv.num_queries
+    rows, paths = arr(v.rows, nq * w), arr(v.paths, nq * pl)
+    return dict(width=w, local=arr(v.local, w), next=arr(v.next, w),
+                rows=[rows[i * w:(i + 1) * w] for i in range(nq)],
+                paths=[paths[i * pl:(i + 1) * pl] for i in range(nq)])
+
+
 @dataclass
 class Commitments:
     trace: np.ndarray            # Hash<Val, Val, 1>: (1, 4)

@@ -142,6 +142,17 @@ def _take_proof(proof: ctypes.c_void_p, size_only: bool = False):
         L.lib().lsp_proof_free(proof)
 
 
+class Preprocessed:
+    """A committed matrix of fixed columns (Context.preprocess): ``commit`` the
+    Merkle root over its LDE, ``width`` its column count, ``tree`` the
+    ``MerkleTree`` over the (h << log_blowup) x width LDE (``MerkleTreeMmcs``
+    opens it, ``tree.layer`` reads its digests; its device memory lives until
+    the tree is dropped), ``cols`` the raw columns (what check_constraints reads)."""
+
+    def __init__(self, tree, commit, width, cols):
+        self.tree, self.commit, self.width, self.cols = tree, commit, width, cols
+
+
 class Context:
     """One lsp_ctx: a GPU, a stream, the Poseidon2 constants and a buffer pool."""
 
@@ -275,7 +286,9 @@ class Context:
 
     # -------------------------------------------------------------- quotient
     def quotient_values(self, lde: np.ndarray, h: int, air: LineaAIR, public_values: np.ndarray,
-                        alpha: np.ndarray) -> np.ndarray:
+                        alpha: np.ndarray, prep_lde: Optional[np.ndarray] = None) -> np.ndarray:
+        """prep_lde: the LDE of the preprocessed matrix, (h << log_blowup, wp, 4), for an
+        AIR that reads preprocessed columns (lsp_quotient_values_preprocessed)"""
         lde = _fr_arr(lde)
         desc = (ctypes.c_int32 * len(air.descriptor()))(*air.descriptor())
         lq = ctypes.c_uint32()
@@ -283,6 +296,14 @@ class Context:
         out = np.zeros((h << lq.value, 4), np.uint64)
         pub = _fr_arr(public_values).reshape(-1, 4)
         al = _fr_arr(alpha).reshape(-1, 4)
+        if prep_lde is not None:
+            pl = _fr_arr(prep_lde)
+            if pl.ndim != 3 or pl.shape[0] != lde.shape[0]:
+                raise ValueError("prep_lde must be (rows of lde, wp, 4)")
+            self._chk(L.lib().lsp_quotient_values_preprocessed(self.h, _ptr(lde), h, lde.shape[1], _ptr(pl),
+                                                               pl.shape[1], desc, len(desc), _ptr(pub), pub.shape[0],
+                                                               _ptr(al), _ptr(out), L.LSP_MEM_HOST))
+            return out
         self._chk(L.lib().lsp_quotient_values(self.h, _ptr(lde), h, lde.shape[1], desc, len(desc), _ptr(pub),
                                               pub.shape[0], _ptr(al), _ptr(out), L.LSP_MEM_HOST))
         return out
@@ -329,12 +350,14 @@ class Context:
 
     # ----------------------------------------------------- check_constraints
     def check_constraints(self, trace, air: LineaAIR, public_values: np.ndarray, h: Optional[int] = None,
-                          w: Optional[int] = None, max_violations: int = 16) -> ConstraintReport:
+                          w: Optional[int] = None, max_violations: int = 16, preprocessed=None) -> ConstraintReport:
         """p3-uni-stark's check_constraints (the reference's debug-build check
         inside prove): which rows of the trace break which constraints.
         `trace` as in prove: an (h, w, 4) host array, or a device pointer (int)
         with h and w given.  A host-only context (device=-1) checks a host
-        array on the CPU."""
+        array on the CPU.  `preprocessed`: the raw (h, wp, 4) matrix of fixed
+        columns, or a ``Preprocessed``, for an AIR that reads them
+        (lsp_check_constraints_preprocessed); the trace is then a host array."""
         desc = (ctypes.c_int32 * len(air.descriptor()))(*air.descriptor())
         pub = _fr_arr(public_values).reshape(-1, 4)
         nc = ctypes.c_uint32()
@@ -348,8 +371,16 @@ class Context:
         else:
             t = _fr_arr(trace)
             tp, h, w, mem = _ptr(t), t.shape[0], t.shape[1], L.LSP_MEM_HOST
-        self._chk(L.lib().lsp_check_constraints(self.h, tp, h, w, desc, len(desc), _ptr(pub), pub.shape[0], mem,
-                                                ctypes.byref(s), counts, firsts, lst, cap, ctypes.byref(nl)))
+        if preprocessed is not None:
+            pm = _fr_arr(preprocessed.cols if isinstance(preprocessed, Preprocessed) else preprocessed)
+            if mem != L.LSP_MEM_HOST or pm.ndim != 3 or pm.shape[0] != h:
+                raise ValueError("preprocessed must be an (h, wp, 4) host array beside a host trace")
+            self._chk(L.lib().lsp_check_constraints_preprocessed(
+                self.h, tp, h, w, _ptr(pm), pm.shape[1], desc, len(desc), _ptr(pub), pub.shape[0], mem,
+                ctypes.byref(s), counts, firsts, lst, cap, ctypes.byref(nl)))
+        else:
+            self._chk(L.lib().lsp_check_constraints(self.h, tp, h, w, desc, len(desc), _ptr(pub), pub.shape[0], mem,
+                                                    ctypes.byref(s), counts, firsts, lst, cap, ctypes.byref(nl)))
         names = air.constraint_names()
         assert len(names) == s.ncons == nc.value
         from .field import from_mont
@@ -379,21 +410,48 @@ class Context:
             out.append(int(d.value))
         return out
 
+    # ---------------------------------------------------------- preprocessed
+    def preprocess(self, cols: np.ndarray) -> "Preprocessed":
+        """lsp_preprocess: commit an (h, wp, 4) matrix of fixed columns once.
+        The result holds the commitment, the width, the tree (its LDE and
+        digests stay on the device while it lives) and the raw columns."""
+        c = _fr_arr(cols)
+        if c.ndim != 3:
+            raise ValueError("cols must be (h, wp, 4)")
+        root, tree = np.zeros((1, 4), np.uint64), ctypes.c_void_p()
+        self._chk(L.lib().lsp_preprocess(self.h, _ptr(c), c.shape[0], c.shape[1], L.LSP_MEM_HOST, _ptr(root),
+                                         ctypes.byref(tree)))
+        height = c.shape[0] << self.config.log_blowup
+        return Preprocessed(MerkleTree(self, tree, height, [c.shape[1]]), root, c.shape[1], c)
+
     # ----------------------------------------------------------------- prove
     def prove(self, trace, air: LineaAIR, public_values: np.ndarray, h: Optional[int] = None,
-              w: Optional[int] = None, check: bool = False) -> bytes:
-        """p3_uni_stark::prove.  `trace` is an (h, w, 4) host array, or a device
+              w: Optional[int] = None, check: bool = False, preprocessed=None) -> bytes:
+        """p3_uni_stark::prove.  preprocessed: a ``Preprocessed`` (or a ``MerkleTree``
+        over one caller-made LDE) for an AIR that reads fixed columns
+        (lsp_prove_preprocessed; the proof is "LSPPRF03").  check=True then needs
+        a ``Preprocessed``, whose raw columns the check reads.  `trace` is an (h, w, 4) host array, or a device
         pointer (int) to an h x w matrix with h and w given.  check=True runs
         check_constraints first and raises ConstraintError(report) instead of
         proving a trace that violates the AIR (a development switch, as the
         reference's debug-build check is)."""
         if check:
-            report = self.check_constraints(trace, air, public_values, h, w)
+            report = self.check_constraints(trace, air, public_values, h, w, preprocessed=preprocessed)
             if not report.ok:
                 raise ConstraintError(report)
         desc = (ctypes.c_int32 * len(air.descriptor()))(*air.descriptor())
         pub = _fr_arr(public_values).reshape(-1, 4)
         proof = ctypes.c_void_p()
+        if preprocessed is not None:
+            tree = preprocessed.tree if isinstance(preprocessed, Preprocessed) else preprocessed
+            if isinstance(trace, int):
+                tp, mem = trace, L.LSP_MEM_DEVICE
+            else:
+                t = _fr_arr(trace)
+                tp, h, w, mem = _ptr(t), t.shape[0], t.shape[1], L.LSP_MEM_HOST
+            self._chk(L.lib().lsp_prove_preprocessed(self.h, tp, h, w, tree.handle, desc, len(desc), _ptr(pub),
+                                                     pub.shape[0], mem, ctypes.byref(proof)))
+            return _take_proof(proof)
         if isinstance(trace, int):
             self._chk(L.lib().lsp_prove(self.h, trace, h, w, desc, len(desc), _ptr(pub), pub.shape[0],
                                         L.LSP_MEM_DEVICE, ctypes.byref(proof)))
@@ -403,10 +461,19 @@ class Context:
                                         pub.shape[0], L.LSP_MEM_HOST, ctypes.byref(proof)))
         return _take_proof(proof)
 
-    def verify(self, proof: bytes, air: LineaAIR, public_values: np.ndarray) -> bool:
+    def verify(self, proof: bytes, air: LineaAIR, public_values: np.ndarray, preprocessed=None) -> bool:
+        """preprocessed: ``(commit, width)`` or a ``Preprocessed`` -- the verifier's
+        data about the AIR's fixed columns, for an "LSPPRF03" proof (lsp_verify_preprocessed)"""
         desc = (ctypes.c_int32 * len(air.descriptor()))(*air.descriptor())
         pub = _fr_arr(public_values).reshape(-1, 4)
-        rc = L.lib().lsp_verify(self.h, desc, len(desc), _ptr(pub), pub.shape[0], proof, len(proof))
+        if preprocessed is not None:
+            commit, width = ((preprocessed.commit, preprocessed.width) if isinstance(preprocessed, Preprocessed)
+                             else preprocessed)
+            c = _fr_arr(commit).reshape(-1, 4)
+            rc = L.lib().lsp_verify_preprocessed(self.h, desc, len(desc), _ptr(pub), pub.shape[0], _ptr(c),
+                                                 int(width), proof, len(proof))
+        else:
+            rc = L.lib().lsp_verify(self.h, desc, len(desc), _ptr(pub), pub.shape[0], proof, len(proof))
         if rc == L.LSP_E_VERIFY:
             return False
         L.check(rc)

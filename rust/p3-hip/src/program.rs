@@ -11,8 +11,11 @@
 //! ```
 //! Public values stay `[alpha, delta, ...]` on the library's side only by
 //! convention of the built-in configs: a program may read any index.
-//! Preprocessed and periodic columns, several trace phases and extension
-//! fields are outside the format.
+//! Periodic columns, several trace phases and extension fields are outside the
+//! format.  Preprocessed columns have a config type of their own on the
+//! library's side (`LSP_AIR_PROGRAM_PREP`, operand kinds 8 `PREP_LOCAL` and 9
+//! `PREP_NEXT`; include/lsp.h), which this lowering does not emit: the fork's
+//! uni-stark has no preprocessed trace, so such an entry stays `Unsupported`.
 use std::collections::HashMap;
 use std::rc::Rc;
 
@@ -31,6 +34,12 @@ const CONST: i32 = 4;
 const FIRST: i32 = 5;
 const LAST: i32 = 6;
 const TRANS: i32 = 7;
+/// `LSP_AIR_PROGRAM_PREP` only (config type 4: `4, width, prep_width, nslots, ...`):
+/// a cell of the preprocessed matrix in the row of `LOCAL` / `NEXT`.  Named here
+/// for readers of a descriptor; `lower` emits neither (see the module comment).
+pub const PREP_LOCAL: i32 = 8;
+pub const PREP_NEXT: i32 = 9;
+pub const PROGRAM_PREP_TYPE: i32 = sys::LSP_AIR_PROGRAM_PREP;
 const ADD: i32 = 1;
 const SUB: i32 = 2;
 const MUL: i32 = 3;

@@ -80,6 +80,12 @@ where
     SC: StarkGenericConfig,
     Proof<SC>: DeserializeOwned,
 {
+    // an LSPPRF03 proof (over an AIR with a preprocessed matrix) has openings the
+    // fork's Proof<SC> has no field for: refused, never converted without them
+    let mut pv = std::mem::MaybeUninit::<sys::lsp_proof_preprocessed_view>::zeroed();
+    if unsafe { sys::lsp_proof_get_preprocessed_view(h, pv.as_mut_ptr()) } == sys::LSP_OK {
+        panic!("to_proof: an LSPPRF03 proof (preprocessed columns) has no Proof<SC> form; carry it as bytes");
+    }
     let mut v = std::mem::MaybeUninit::<sys::lsp_proof_view>::zeroed();
     check_global(unsafe { sys::lsp_proof_get_view(h, v.as_mut_ptr()) }, "lsp_proof_get_view");
     let v = unsafe { v.assume_init() };

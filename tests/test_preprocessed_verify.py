@@ -1,0 +1,212 @@
+"""lsp_verify_preprocessed on the CPU (host-only context) against the
+independent big-integer prover of tests/preprocessed_ref.py: reference proofs
+("LSPPRF03") over AIRs that read preprocessed columns are accepted under every
+transcript switch, and a wrong commitment, a wrong width, a flipped byte in any
+of the preprocessed fields and either format where the other is expected are
+rejected.  The reference prover itself is held to the existing verifier through
+layout "a" (every column in the main trace, "LSPPRF02")."""
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+import preprocessed_ref as PR  # noqa: E402
+from linea_stark_prover_amd.field import MODULUS, to_mont  # noqa: E402
+from oracle import pyoracle as O  # noqa: E402
+
+# wp = 1, 2, 1 (w = 3 > wp), 9, 3, 5 at h = 2, 4, 32
+SHAPES = [("keyed", 2), ("gated", 4), ("wide", 4), ("pressure", 32), ("keys3", 4), ("keys5", 32)]
+SWITCHES = ["skip_log_degree", "skip_public_values", "observe_opened_values", "sample_bits_montgomery",
+            "skip_final_poly"]
+
+
+def _fri(switch):
+    return O.FriParams(observe_log_degree=switch != "skip_log_degree",
+                       observe_public_values=switch != "skip_public_values",
+                       observe_opened_values=switch == "observe_opened_values",
+                       sample_bits_montgomery=switch == "sample_bits_montgomery",
+                       observe_final_poly=switch != "skip_final_poly")
+
+
+@pytest.fixture(scope="module")
+def env(product_lib):
+    from linea_stark_prover_amd import _lib as L
+    from linea_stark_prover_amd import prover as P
+    ctxs = {}
+
+    def ctx(switch=None):
+        if switch not in ctxs:
+            ctxs[switch] = P.Context(P.StarkConfig(**({switch: True} if switch else {})), device=-1)
+        return ctxs[switch]
+    yield dict(L=L, ctx=ctx, s=O.setup_from_seed())
+    for c in ctxs.values():
+        c.close()
+
+
+@pytest.fixture(scope="module")
+def proofs(env):
+    """(name, h, layout, switch) -> (proof, log, air, pub ints), each made once"""
+    cache = {}
+
+    def get(name, h, layout="b", switch=None):
+        key = (name, h, layout, switch)
+        if key not in cache:
+            s = env["s"]
+            fixed, main, extra = PR.build_rows(name, h)
+            pubi = [s.alpha, s.delta] + extra
+            air = PR.build_air(name, layout)
+            if layout == "a":
+                proof, log = PR.prove(air, PR.joined(fixed, main), None, pubi, s.perm, _fri(switch))
+            else:
+                proof, log = PR.prove(air, main, fixed, pubi, s.perm, _fri(switch))
+            cache[key] = (proof, log, air, pubi)
+        return cache[key]
+    return get
+
+
+def _pre(log, wp):
+    return (to_mont([log["prep_root"]]), wp)
+
+
+@pytest.mark.parametrize("name,h", SHAPES)
+def test_the_reference_prover_is_held_to_the_existing_verifier(env, proofs, name, h):
+    proof, log, air, pubi = proofs(name, h, "a")
+    assert proof[:8] == b"LSPPRF02" and log["log_q"] == PR.LOG_Q[name]
+    assert env["ctx"]().verify(proof, air, to_mont(pubi))
+    bad = list(pubi)
+    bad[2] = (bad[2] + 1) % MODULUS
+    assert not env["ctx"]().verify(proof, air, to_mont(bad))
+
+
+@pytest.mark.parametrize("name,h", SHAPES)
+def test_reference_proofs_are_accepted(env, proofs, name, h):
+    proof, log, air, pubi = proofs(name, h)
+    wp = PR.AIRS[name][0]
+    assert proof[:8] == b"LSPPRF03"
+    assert env["ctx"]().verify(proof, air, to_mont(pubi), preprocessed=_pre(log, wp))
+    bad = list(pubi)
+    bad[2] = (bad[2] + 1) % MODULUS
+    assert not env["ctx"]().verify(proof, air, to_mont(bad), preprocessed=_pre(log, wp))
+
+
+@pytest.mark.parametrize("switch", SWITCHES)
+def test_each_transcript_switch(env, proofs, switch):
+    proof, log, air, pubi = proofs("gated", 4, "b", switch)
+    pub, pre = to_mont(pubi), _pre(log, 2)
+    assert env["ctx"](switch).verify(proof, air, pub, preprocessed=pre)
+    assert not env["ctx"]().verify(proof, air, pub, preprocessed=pre)  # the default transcript is another
+    assert proof != proofs("gated", 4)[0]
+
+
+@pytest.mark.parametrize("name,h", SHAPES)
+def test_rejections(env, proofs, name, h):
+    L, ctx = env["L"], env["ctx"]()
+    proof, log, air, pubi = proofs(name, h)
+    wp, pub = PR.AIRS[name][0], to_mont(pubi)
+    pre = _pre(log, wp)
+    assert ctx.verify(proof, air, pub, preprocessed=pre)
+    # the commitment and the width are the verifier's own: wrong ones reject
+    assert not ctx.verify(proof, air, pub, preprocessed=(to_mont([(log["prep_root"] + 1) % MODULUS]), wp))
+    other = PR.preprocess([[x + 1 for x in r] for r in PR.build_rows(name, h)[0]], env["s"].perm)[1].root
+    assert not ctx.verify(proof, air, pub, preprocessed=(to_mont([other]), wp))
+    assert not ctx.verify(proof, air, pub, preprocessed=(pre[0], wp + 1))
+    with pytest.raises(L.LspError) as e:  # fewer columns than the AIR reads: not a proof question
+        ctx.verify(proof, air, pub, preprocessed=(pre[0], wp - 1))
+    assert e.value.code == L.LSP_E_ARG
+    # one flipped byte in each preprocessed field
+    for field, at in sorted(log["marks"].items()):
+        for off in (0, 31) if "path" not in field else (4, 35):
+            data = bytearray(proof)
+            data[at + off] ^= 0x01
+            assert not ctx.verify(bytes(data), air, pub, preprocessed=pre), (field, off)
+    # the format crossings
+    plain, _, air_a, pub_a = proofs(name, h, "a")
+    with pytest.raises(L.LspError) as e:  # the AIR needs a commitment lsp_verify is not given
+        ctx.verify(proof, air, pub)
+    assert e.value.code == L.LSP_E_ARG
+    assert not ctx.verify(proof, air_a, pub)                               # LSPPRF03 bytes to lsp_verify
+    assert not ctx.verify(plain, air, pub, preprocessed=pre)               # LSPPRF02 bytes here
+    assert not ctx.verify(plain, air_a, to_mont(pub_a), preprocessed=pre)  # ... also with the AIR they were made for
+    assert not ctx.verify(b"LSPPRF02" + proof[8:], air, pub, preprocessed=pre)
+    assert not ctx.verify(b"LSPPRF03" + plain[8:], air_a, to_mont(pub_a), preprocessed=pre)
+
+
+def test_truncations_and_mutations_return_a_status():
+    r = subprocess.run([sys.executable, os.path.join(HERE, "preprocessed_fuzz_child.py")], capture_output=True,
+                       text=True, timeout=600)
+    lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+    assert r.returncode == 0 and lines and lines[-1].get("done"), (lines[-1:] if lines else None, r.stderr[-2000:])
+    assert lines[-1]["accepted"] == 0 and lines[-1]["rejected"] > 700
+    assert lines[-1]["unparsed"] > 400 and lines[-1]["parsed"] + lines[-1]["unparsed"] == lines[-1]["rejected"]
+
+
+# ------------------------------------------------------------------- wire
+def _handle(L, data):
+    import ctypes
+    h = ctypes.c_void_p()
+    L.check(L.lib().lsp_proof_deserialize(data, len(data), ctypes.byref(h)))
+    return h
+
+
+@pytest.mark.parametrize("layout", ["a", "b"])
+@pytest.mark.parametrize("name,h", SHAPES)
+def test_deserialize_serialize_is_the_identity_and_the_views_are_the_references_parse(env, proofs, name, h, layout):
+    from linea_stark_prover_amd.field import from_mont
+    from linea_stark_prover_amd.proof import Proof, preprocessed_openings
+    from linea_stark_prover_amd.prover import _take_proof
+    L = env["L"]
+    data = proofs(name, h, layout)[0]
+    ref = PR.parse(data)
+    hd = _handle(L, data)
+    try:
+        view = Proof.from_handle(hd)
+        if layout == "b":
+            pv = preprocessed_openings(hd)
+        else:
+            with pytest.raises(L.LspError) as e:  # an LSPPRF02 proof has none
+                preprocessed_openings(hd)
+            assert e.value.code == L.LSP_E_STATE
+    finally:
+        assert _take_proof(hd) == data  # (frees the handle)
+    ints = lambda a: from_mont(a)  # noqa: E731
+    fp, ov = view.opening_proof, view.opened_values
+    assert view.degree_bits == ref["log_h"]
+    assert ints(view.commitments.trace) == [ref["trace_root"]]
+    assert ints(view.commitments.quotient_chunks) == [ref["quotient_root"]]
+    assert ints(ov.trace_local) == ref["trace_local"] and ints(ov.trace_next) == ref["trace_next"]
+    assert [ints(c)[0] for c in ov.quotient_chunks] == ref["chunks"]
+    assert ints(fp.commit_phase_commits) == ref["fri_roots"] and ints(fp.final_poly) == ref["final_poly"]
+    assert ints(fp.pow_witness.reshape(1, 4)) == [ref["pow_witness"]]
+    assert len(fp.query_proofs) == len(ref["queries"]) == 33
+    for qp, rq in zip(fp.query_proofs, ref["queries"]):
+        t, qo = qp.input_proof
+        assert ints(t.opened_values[0]) == rq["trow"] and ints(t.opening_proof) == rq["tpath"]
+        assert [ints(x)[0] for x in qo.opened_values] == rq["qrow"] and ints(qo.opening_proof) == rq["qpath"]
+        assert [(ints(s.sibling_value.reshape(1, 4))[0], ints(s.opening_proof)) for s in qp.commit_phase_openings] \
+            == rq["steps"]
+    if layout == "b":
+        assert pv["width"] == ref["wp"] == PR.AIRS[name][0]
+        assert ints(pv["local"]) == ref["prep_local"] and ints(pv["next"]) == ref["prep_next"]
+        assert [ints(r) for r in pv["rows"]] == [rq["prow"] for rq in ref["queries"]]
+        assert [ints(p) for p in pv["paths"]] == [rq["ppath"] for rq in ref["queries"]]
+
+
+def test_deserialize_range_checks_the_preprocessed_width(env, proofs):
+    import ctypes
+    import struct
+    L = env["L"]
+    data = proofs("gated", 4)[0]
+    for wp in (0, 1, 3, (1 << 20) + 1, 0xFFFFFFFF):  # header word 7: prep_width (2 in this proof)
+        bad = data[:32] + struct.pack("<I", wp) + data[36:]
+        h = ctypes.c_void_p()
+        assert L.lib().lsp_proof_deserialize(bad, len(bad), ctypes.byref(h)) == L.LSP_E_ARG, wp
+    for magic in (b"LSPPRF01", b"LSPPRF04", b"LSPPRF02"):
+        h = ctypes.c_void_p()
+        bad = magic + data[8:]
+        assert L.lib().lsp_proof_deserialize(bad, len(bad), ctypes.byref(h)) == L.LSP_E_ARG, magic
