@@ -223,6 +223,35 @@ def build_rows(name, h, x0=5):
     return fixed, main, [-sum((i + 2) ** 2 for i in range(n)) % R]
 
 
+def keyed_sum(wp):
+    """x' = x^2 + fixed[0] + ... + fixed[wp - 1] on one main column (layout b
+    only), the sum running in the one slot that held x^2: the program reads
+    every preprocessed column, so prep_width = wp at any width, and its
+    register file stays one slot.  x starts at public value 2.  Degree 2."""
+    b = ProgramBuilder(1, preprocessed_width=wp)
+    x, s = b.local[0], b.local[0] * b.local[0]
+    for i in range(wp):
+        s = s + b.preprocessed[i]
+    b.when_first_row().assert_eq(x, b.public[2], "x starts at x0")
+    b.when_transition().assert_eq(b.next[0], s, "x' = x^2 + sum fixed")
+    cfg = b.build()
+    assert cfg.nslots == 1 and cfg.prep_width == wp, (cfg.nslots, cfg.prep_width)
+    return LineaAIR([cfg])
+
+
+def keyed_sum_rows(wp, h, x0=5):
+    """(fixed rows h x wp, main rows h x 1, the public values after [alpha,
+    delta]) of a trace that satisfies keyed_sum(wp); the fixed cells differ in
+    every row and column and reach the top limb"""
+    fixed = [[(R - 1 - 7 * j * j - 3 - 11 * i * (i + 1)) % R if (i + j) % 3 == 0 else (7 * j * j + 3 + 11 * i) % R
+              for i in range(wp)] for j in range(h)]
+    main, x = [], x0
+    for j in range(h):
+        main.append([x])
+        x = (x * x + sum(fixed[j])) % R
+    return fixed, main, [x0]
+
+
 def joined(fixed, main):
     """layout a's trace rows: the fixed columns first"""
     return [list(f) + list(m) for f, m in zip(fixed, main)]

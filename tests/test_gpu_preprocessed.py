@@ -313,3 +313,101 @@ def test_unfit_trees_are_refused(gpu_ctx):
     proof = gpu_ctx.prove(trace, air, pub, preprocessed=own)
     assert gpu_ctx.verify(proof, air, pub, preprocessed=(root, 2))
     assert proof == gpu_ctx.prove(trace, air, pub, preprocessed=gpu_ctx.preprocess(PR.to_matrix(fixed)))
+
+
+# ------------------------------------------------------ k_reduce_prep's edges
+# The kernel that adds the preprocessed matrix's terms to the FRI input loads a
+# row in chunks of three columns (RR_CHUNK), one chunk ahead, and keeps the wp
+# alpha powers in dynamic LDS behind the 3 KiB reduction table: 36 bytes a
+# column, over 48 KiB from wp = 1281 (asked for by attribute), refused past the
+# device's LDS per workgroup.  PR.keyed_sum(wp) reads every one of wp columns
+# in one slot, so only this kernel's limits are in play.
+QTAB_BYTES, APW_BYTES = 3 * 64 * 16, 36
+
+
+@pytest.fixture(scope="module")
+def keyed_sum_reference():
+    """(wp, h) -> (the big-integer prover's proof, its log, fixed, main, pub ints), made once"""
+    cache = {}
+
+    def get(wp, h):
+        if (wp, h) not in cache:
+            s = _setup()
+            fixed, main, extra = PR.keyed_sum_rows(wp, h)
+            pubi = [s.alpha, s.delta] + extra
+            proof, log = PR.prove(PR.keyed_sum(wp), main, fixed, pubi, s.perm)
+            cache[(wp, h)] = (proof, log, fixed, main, pubi)
+        return cache[(wp, h)]
+    return get
+
+
+@pytest.mark.parametrize("wp,h", [(2, 4), (3, 4), (4, 4), (5, 4), (6, 4), (7, 4), (7, 64)])
+def test_chunk_boundaries_of_the_prep_reduction(gpu_ctx, keyed_sum_reference, wp, h):
+    """widths below, at and above one and two chunks of three, byte for byte;
+    h = 64: 512 LDE rows, two blocks"""
+    exp, log, fixed, main, pubi = keyed_sum_reference(wp, h)
+    air, pub = PR.keyed_sum(wp), to_mont(pubi)
+    pre = gpu_ctx.preprocess(PR.to_matrix(fixed))
+    assert pre.width == wp and from_mont(pre.commit)[0] == log["prep_root"]
+    got = gpu_ctx.prove(PR.to_matrix(main), air, pub, preprocessed=pre)
+    assert got == exp
+    assert gpu_ctx.verify(got, air, pub, preprocessed=pre)
+
+
+def test_prep_reduction_over_48_kib_of_lds(gpu_ctx, keyed_sum_reference):
+    wp, h = 1300, 2
+    assert QTAB_BYTES + APW_BYTES * wp > 48 * 1024 >= QTAB_BYTES + APW_BYTES * 1280
+    exp, log, fixed, main, pubi = keyed_sum_reference(wp, h)
+    air, pub = PR.keyed_sum(wp), to_mont(pubi)
+    pre = gpu_ctx.preprocess(PR.to_matrix(fixed))
+    got = gpu_ctx.prove(PR.to_matrix(main), air, pub, preprocessed=pre)
+    assert got == exp
+    assert gpu_ctx.verify(got, air, pub, preprocessed=pre)
+    for col in (0, wp - 1):  # a flipped opened preprocessed value, the first and the last column
+        flipped = bytearray(got)
+        flipped[log["marks"]["prep_local"] + 32 * col + 3] ^= 0x10
+        assert not gpu_ctx.verify(bytes(flipped), air, pub, preprocessed=pre)
+
+
+def _lds_per_workgroup():
+    """hipDeviceProp_t::sharedMemPerBlock of device 0 (what the context's
+    hipDeviceAttributeMaxSharedMemoryPerBlock query answers), from the runtime
+    the library has loaded"""
+    import ctypes
+    hip = ctypes.CDLL("libamdhip64.so")
+    prop = ctypes.create_string_buffer(8192)
+    assert hip.hipGetDevicePropertiesR0600(prop, 0) == 0
+    return int.from_bytes(prop.raw[296:304], "little")  # after name[256], uuid, luid, the mask, totalGlobalMem
+
+
+def test_refusal_boundary_of_the_prep_reduction(gpu_ctx):
+    """the widest matrix reduce_prep_fits allows proves and verifies, one
+    column more is LSP_E_ARG and leaves the context usable"""
+    from linea_stark_prover_amd import _lib as L
+    from linea_stark_prover_amd import prover as P
+    from linea_stark_prover_amd.air import permutation_air
+    lds = _lds_per_workgroup()
+    assert lds in (64 * 1024, 160 * 1024), lds
+    wp_max = (lds - QTAB_BYTES) // APW_BYTES
+    if lds == 160 * 1024:  # gfx950
+        assert wp_max == 4465
+    h = 2
+    a, d, _ = gpu_ctx.config.seeded()
+    for wp in (wp_max + 1, wp_max):
+        fixed, main, extra = PR.keyed_sum_rows(wp, h)
+        pubi, pub = _pubs(gpu_ctx, extra)
+        air = PR.keyed_sum(wp)
+        assert PR.report(air, main, pubi, 4, fixed)["ok"]
+        pre = gpu_ctx.preprocess(PR.to_matrix(fixed))
+        if wp > wp_max:
+            with pytest.raises(L.LspError, match="wider than the reduce kernel's LDS holds") as e:
+                gpu_ctx.prove(PR.to_matrix(main), air, pub, preprocessed=pre)
+            assert e.value.code == L.LSP_E_ARG
+            # the context proves an ordinary trace afterwards
+            tr = P.gen_permutation_trace(5, 2, a, d)
+            pub2 = np.concatenate([a, d])
+            assert gpu_ctx.verify(gpu_ctx.prove(tr, permutation_air(2), pub2), permutation_air(2), pub2)
+        else:
+            proof = gpu_ctx.prove(PR.to_matrix(main), air, pub, preprocessed=pre)
+            assert gpu_ctx.verify(proof, air, pub, preprocessed=pre)
+            assert not gpu_ctx.verify(proof, air, pub, preprocessed=(pre.commit, wp + 1))
