@@ -418,14 +418,18 @@ int lsp_check_constraints_preprocessed(lsp_ctx *ctx, const lsp_fr *trace, size_t
 
 /* ------------------------------------------------------------- PCS open */
 /* interpolate_coset [EXT p3-interpolation] of the first h rows of a bit-reversed
- * LDE (the low coset shift*H_h) at z: ys_out gets w values (host memory). */
+ * LDE (the low coset shift*H_h) at z: ys_out gets w values (host memory).
+ * LSP_E_ARG if shift is zero or z lies on the coset (z^h = shift^h): there the
+ * barycentric formula divides by zero (p3 panics); the value is the row itself. */
 int lsp_interpolate_coset(lsp_ctx *ctx, const lsp_fr *lde_bitrev, size_t h, size_t w, const lsp_fr *shift,
                           const lsp_fr *z, lsp_fr *ys_out, int mem);
 /* compute_inverse_denominators of TwoAdicFriPcs::open [EXT p3-fri], reached
  * from p3_uni_stark::prove (bin/src/main.rs:80-86) through pcs.open:
  * out[p*N + i] = 1 / (points[p] - shift * w_N^bitrev(i)), N = 2^log_n, i.e.
  * against the bit-reversed LDE domain shift*H_N (shift = GENERATOR there).
- * Every point must lie outside that coset.  out: npoints * N elements. */
+ * Every point must lie outside that coset: LSP_E_ARG, before anything is
+ * computed, if shift is zero or some points[p]^N = shift^N (p3 panics there).
+ * out: npoints * N elements. */
 int lsp_inverse_denominators(lsp_ctx *ctx, const lsp_fr *points, size_t npoints, uint32_t log_n,
                              const lsp_fr *shift, lsp_fr *out, int mem);
 /* The "reduce rows" step of TwoAdicFriPcs::open [EXT p3-fri] for one matrix
@@ -446,7 +450,9 @@ int lsp_open_reduce(lsp_ctx *ctx, const lsp_fr *mat, size_t n, size_t w, const l
  * context. */
 int lsp_host_compress_batch(const lsp_ctx *ctx, const lsp_fr *pairs, size_t n, lsp_fr *out);
 int lsp_host_hash_rows(const lsp_ctx *ctx, const lsp_fr *rows, size_t n, size_t w, lsp_fr *out);
-/* p3-field batch_multiplicative_inverse */
+/* p3-field batch_multiplicative_inverse: out[i] = 1 / in[i].  A zero input
+ * gives a zero output and leaves every other element's inverse as it is (p3
+ * panics on a zero).  out must not be in. */
 int lsp_batch_inverse(lsp_ctx *ctx, const lsp_fr *in, size_t n, lsp_fr *out, int mem);
 
 /* ----------------------------------------------------------------- prove */
@@ -666,7 +672,10 @@ int lsp_last_spans(const lsp_ctx *ctx, const char **lines, size_t cap, size_t *n
  *   lookup block: a.., b.., a_filter, b_filters.., a_inverses, b_inverses..,
  *                 multiplicities.., prefix sum                (na + nt(nbc+3) + 3)
  * LSP_E_STATE if the check column does not end at 1 (permutation) / 0
- * (lookup), as the reference asserts.  mem applies to every pointer. */
+ * (lookup), as the reference asserts, and -- "tried to invert zero" -- if some
+ * row combination + delta is 0 (a B row of a permutation; any A or table row
+ * of a lookup, disabled rows included), where the reference panics in
+ * Field::inverse.  mem applies to every pointer. */
 int lsp_witness_permutation(lsp_ctx *ctx, const lsp_fr *a, uint32_t na, const lsp_fr *b, uint32_t nb, size_t n,
                             const lsp_fr *alpha, const lsp_fr *delta, lsp_fr *trace, size_t trace_w, size_t col0,
                             int mem);

@@ -708,6 +708,20 @@ int lsp_quotient_values_preprocessed(lsp_ctx* ctx, const lsp_fr* lde, size_t h, 
     return quotient_values(ctx, lde, h, w, prep_lde, wp, air, air_len, pubv, npub, alpha, out, mem);
 }
 
+extern "C++" {
+namespace {
+// The open stage divides by z - x for every x of the coset shift * H_N: a
+// point on the coset (z^N = shift^N) has no inverse denominators, and p3
+// panics there.  Two host powers, before anything is launched.
+void require_off_coset(const Fr& shift, const Fr* points, size_t npoints, size_t N) {
+    LSP_REQUIRE(!fr_is_zero(fr_to_canonical(shift)), LSP_E_ARG, "coset shift must be nonzero");
+    const Fr sN = fr_pow_u64(shift, N);
+    for (size_t p = 0; p < npoints; ++p)
+        LSP_REQUIRE(!fr_eq(fr_pow_u64(points[p], N), sN), LSP_E_ARG, "a point lies on the coset");
+}
+}  // namespace
+}
+
 int lsp_interpolate_coset(lsp_ctx* ctx, const lsp_fr* lde_bitrev, size_t h, size_t w, const lsp_fr* shift,
                           const lsp_fr* z, lsp_fr* ys_out, int mem) {
     return guarded(ctx, [&] {
@@ -715,8 +729,9 @@ int lsp_interpolate_coset(lsp_ctx* ctx, const lsp_fr* lde_bitrev, size_t h, size
         std::lock_guard<std::mutex> g(ctx->mu);
         need_gpu(ctx);
         const uint32_t logh = log2_exact(h);
-        const Fr* dm = dev_in(ctx, lde_bitrev, h * w, mem, "api_in");
         const Fr S = to_fr(*shift), Z = to_fr(*z);
+        require_off_coset(S, &Z, 1, h);
+        const Fr* dm = dev_in(ctx, lde_bitrev, h * w, mem, "api_in");
         Fr* inv = ctx->fbuf("o_invz", h);
         Fr* sums = ctx->fbuf("o_sums", w);
         open_denominators(ctx, Z, S, logh, 0, h, inv);
@@ -770,9 +785,11 @@ int lsp_inverse_denominators(lsp_ctx* ctx, const lsp_fr* points, size_t npoints,
         std::lock_guard<std::mutex> g(ctx->mu);
         need_gpu(ctx);
         const size_t N = (size_t)1 << log_n;
+        const std::vector<Fr> pts = to_frs(points, npoints);
+        require_off_coset(to_fr(*shift), pts.data(), npoints, N);
         Fr* dout = dev_out(ctx, out, npoints * N, mem, "api_out");
         for (size_t p = 0; p < npoints; ++p)
-            open_denominators(ctx, to_fr(points[p]), to_fr(*shift), log_n, 0, N, dout + p * N);
+            open_denominators(ctx, pts[p], to_fr(*shift), log_n, 0, N, dout + p * N);
         finish_out(ctx, out, dout, npoints * N, mem);
     });
 }

@@ -19,6 +19,8 @@ namespace {
 //   down  workgroup b rebuilds its tree (a thread's chunk product is its last
 //         prefix times its last element), takes 1/prod[b] down the tree and
 //         walks every chunk backwards.
+// A zero input stands as 1 in every product and gets 0 as its output (0 -> 0,
+// the other elements unaffected), so no product at any level is ever 0.
 // Cost ~3 products per element plus one inversion for the whole batch; one
 // level per 4096x (2^22 elements: up, base, down -- three launches; the
 // per-thread chains of the earlier 16x levels took seven).
@@ -26,6 +28,18 @@ constexpr uint32_t BI_THREADS = 256;
 constexpr uint32_t BI_CHUNK = 16;
 constexpr uint32_t BI_WG = BI_THREADS * BI_CHUNK;  // elements per workgroup of the up/down passes
 constexpr uint32_t BI_BASE = BI_THREADS * 16;
+
+// the factor an input contributes to the products: itself, or 1 for a zero
+__device__ __forceinline__ Fr bi_factor(const Fr& x) { return fr_is_zero(x) ? fr_one() : x; }
+
+// one step of a back pass: out[i] holds the prefix product before in[i], inv
+// 1/(the prefix after it); a zero input takes 0, not the inverse of its factor
+__device__ __forceinline__ void bi_back(const Fr* __restrict__ in, Fr* __restrict__ out, size_t i, Fr& inv) {
+    const Fr x = in[i];
+    const Fr o = fr_mul(inv, out[i]);
+    inv = fr_mul(inv, bi_factor(x));
+    out[i] = fr_is_zero(x) ? fr_zero() : o;
+}
 
 // the product tree of a workgroup's 256 chunk products (node k: children 2k,
 // 2k+1; leaves at BI_THREADS + t); ends with a barrier
@@ -67,7 +81,7 @@ __global__ __launch_bounds__(BI_THREADS) void k_bi_up(const Fr* __restrict__ in,
         const size_t i = base + (size_t)j * BI_THREADS;
         if (i >= n) break;
         out[i] = acc;
-        acc = fr_mul(acc, in[i]);
+        acc = fr_mul(acc, bi_factor(in[i]));
     }
     bi_tree_up(tree, t, acc);
     if (t == 0) prod[blockIdx.x] = tree[1];
@@ -82,19 +96,14 @@ __global__ __launch_bounds__(BI_THREADS) void k_bi_down(const Fr* __restrict__ i
     Fr acc = fr_one();
     if (cnt) {
         const size_t il = base + (size_t)(cnt - 1) * BI_THREADS;
-        acc = fr_mul(out[il], in[il]);  // the chunk's product: its last prefix times its last element
+        acc = fr_mul(out[il], bi_factor(in[il]));  // the chunk's product: its last prefix times its last factor
     }
     bi_tree_up(tree, t, acc);
     if (t == 0) tree[1] = inv_prod[blockIdx.x];
     __syncthreads();
     bi_tree_down(tree, t);
     Fr inv = tree[BI_THREADS + t];
-    for (uint32_t j = cnt; j-- > 0;) {
-        const size_t i = base + (size_t)j * BI_THREADS;
-        const Fr o = fr_mul(inv, out[i]);
-        inv = fr_mul(inv, in[i]);
-        out[i] = o;
-    }
+    for (uint32_t j = cnt; j-- > 0;) bi_back(in, out, base + (size_t)j * BI_THREADS, inv);
 }
 
 // a^(r-2) on the 29-bit multiplier (Fermat; the inverse of zero is zero)
@@ -125,7 +134,7 @@ __global__ __launch_bounds__(BI_THREADS) void k_bi_base(const Fr* __restrict__ i
     Fr acc = fr_one();
     for (size_t i = t; i < n; i += BI_THREADS) {
         out[i] = acc;
-        acc = fr_mul(acc, in[i]);
+        acc = fr_mul(acc, bi_factor(in[i]));
     }
     bi_tree_up(tree, t, acc);
     if (t == 0) tree[1] = have_inv ? inv_total : fr_inv_f29(tree[1]);
@@ -135,37 +144,8 @@ __global__ __launch_bounds__(BI_THREADS) void k_bi_base(const Fr* __restrict__ i
     if (t >= n) return;
     const size_t last = t + ((n - 1 - t) / BI_THREADS) * BI_THREADS;
     for (size_t i = last;; i -= BI_THREADS) {
-        const Fr o = fr_mul(inv, out[i]);
-        inv = fr_mul(inv, in[i]);
-        out[i] = o;
+        bi_back(in, out, i, inv);
         if (i < BI_THREADS) break;
-    }
-}
-
-// single-level kernel (no scratch): one Fermat inverse per thread
-// Thread t owns elements t, t+T, t+2T, ... (`chunk` of them, interleaved so every
-// pass is coalesced): a prefix product, one Fermat inverse, the back pass.  The
-// inverse (~380 products) is one instruction stream per wave whatever the
-// chunk, so the launcher sizes the chunk for about one wave per SIMD.
-__global__ __launch_bounds__(256) void k_batch_inverse(const Fr* __restrict__ in, Fr* __restrict__ out, size_t n,
-                                                       size_t T, uint32_t chunk) {
-    const size_t t = gtid();
-    if (t >= T) return;
-    Fr acc = fr_one();
-    uint32_t cnt = 0;
-    for (uint32_t j = 0; j < chunk; ++j) {
-        const size_t i = t + (size_t)j * T;
-        if (i >= n) break;
-        out[i] = acc;
-        acc = fr_mul(acc, in[i]);
-        ++cnt;
-    }
-    Fr inv = fr_inv(acc);
-    for (uint32_t j = cnt; j-- > 0;) {
-        const size_t i = t + (size_t)j * T;
-        const Fr o = fr_mul(inv, out[i]);
-        inv = fr_mul(inv, in[i]);
-        out[i] = o;
     }
 }
 
@@ -220,14 +200,6 @@ size_t batch_inverse_scratch(size_t n) {
 
 hipError_t launch_batch_inverse(const Fr* in, Fr* out, size_t n, hipStream_t st, Fr* scratch, const Fr* inv_total) {
     if (!n) return hipSuccess;
-    if (!scratch && n > BI_BASE) {
-        // lanes for one wave per SIMD (256 CUs x 4 SIMDs x 64), 8 .. 256 elements each
-        uint32_t chunk = 8;
-        while (chunk < 256 && (size_t)chunk * 65536 < n) chunk *= 2;
-        const size_t T = (n + chunk - 1) / chunk;
-        hipLaunchKernelGGL(k_batch_inverse, dim3(nblocks(T, 256)), dim3(256), 0, st, in, out, n, T, chunk);
-        return hipGetLastError();
-    }
     if (n <= BI_BASE) {
         hipLaunchKernelGGL(k_bi_base, dim3(1), dim3(BI_THREADS), 0, st, in, out, n, inv_total ? *inv_total : fr_zero(),
                            inv_total ? 1 : 0);

@@ -126,7 +126,8 @@ __device__ __forceinline__ bool fr_nonzero(const Fr& x) {
 
 __global__ __launch_bounds__(256) void k_perm_rows(const Fr* __restrict__ a, uint32_t na, const Fr* __restrict__ b,
                                                    uint32_t nb, size_t n, Fr alpha, Fr delta, Fr* __restrict__ out,
-                                                   size_t ostride, Fr* __restrict__ al, Fr* __restrict__ bl) {
+                                                   size_t ostride, Fr* __restrict__ al, Fr* __restrict__ bl,
+                                                   uint32_t* __restrict__ zflag) {
     const size_t i = gtid();
     if (i >= n) return;
     Fr* row = out + i * ostride;
@@ -143,15 +144,18 @@ __global__ __launch_bounds__(256) void k_perm_rows(const Fr* __restrict__ a, uin
         row[na + k] = v;
         acc = fr_add(fr_mul(acc, alpha), v);
     }
-    bl[i] = fr_add(acc, delta);
+    const Fr d = fr_add(acc, delta);
+    bl[i] = d;
+    if (!fr_nonzero(d)) atomicOr(zflag, 1u);
 }
 
-// comb[0][i] = A row combination, comb[1+t][i] = table t's; den = comb + delta
+// comb[0][i] = A row combination, comb[1+t][i] = table t's; den = comb + delta;
+// *zflag becomes nonzero if some den is 0 (a denominator the reference cannot invert)
 __global__ __launch_bounds__(256) void k_lookup_rows(const Fr* __restrict__ a, uint32_t na, const Fr* __restrict__ b,
                                                      uint32_t nt, uint32_t nbc, const Fr* __restrict__ afil,
                                                      const Fr* __restrict__ bfil, size_t n, Fr alpha, Fr delta,
                                                      Fr* __restrict__ out, size_t ostride, Fr* __restrict__ comb,
-                                                     Fr* __restrict__ den) {
+                                                     Fr* __restrict__ den, uint32_t* __restrict__ zflag) {
     const size_t i = gtid();
     if (i >= n) return;
     Fr* row = out + i * ostride;
@@ -162,7 +166,9 @@ __global__ __launch_bounds__(256) void k_lookup_rows(const Fr* __restrict__ a, u
         acc = fr_add(fr_mul(acc, alpha), v);
     }
     comb[i] = acc;
-    den[i] = fr_add(acc, delta);
+    Fr d = fr_add(acc, delta);
+    den[i] = d;
+    bool zero = !fr_nonzero(d);
     for (uint32_t t = 0; t < nt; ++t) {
         acc = fr_zero();
         for (uint32_t k = 0; k < nbc; ++k) {
@@ -171,8 +177,11 @@ __global__ __launch_bounds__(256) void k_lookup_rows(const Fr* __restrict__ a, u
             acc = fr_add(fr_mul(acc, alpha), v);
         }
         comb[(1 + (size_t)t) * n + i] = acc;
-        den[(1 + (size_t)t) * n + i] = fr_add(acc, delta);
+        d = fr_add(acc, delta);
+        den[(1 + (size_t)t) * n + i] = d;
+        zero |= !fr_nonzero(d);
     }
+    if (zero) atomicOr(zflag, 1u);
     const uint32_t f0 = na + nt * nbc;
     row[f0] = afil[i];
     for (uint32_t t = 0; t < nt; ++t) row[f0 + 1 + t] = bfil[(size_t)t * n + i];
@@ -344,17 +353,17 @@ hipError_t launch_gen_raw_perm(uint64_t seed, size_t n, uint32_t ncols, uint64_t
 }
 
 hipError_t launch_perm_rows(const Fr* a, uint32_t na, const Fr* b, uint32_t nb, size_t n, Fr alpha, Fr delta,
-                            Fr* out, size_t ostride, Fr* al, Fr* bl, hipStream_t st) {
+                            Fr* out, size_t ostride, Fr* al, Fr* bl, uint32_t* zflag, hipStream_t st) {
     hipLaunchKernelGGL(k_perm_rows, dim3(nblocks(n, 256)), dim3(256), 0, st, a, na, b, nb, n, alpha, delta, out,
-                       ostride, al, bl);
+                       ostride, al, bl, zflag);
     return hipGetLastError();
 }
 
 hipError_t launch_lookup_rows(const Fr* a, uint32_t na, const Fr* b, uint32_t nt, uint32_t nbc, const Fr* afil,
                               const Fr* bfil, size_t n, Fr alpha, Fr delta, Fr* out, size_t ostride, Fr* comb,
-                              Fr* den, hipStream_t st) {
+                              Fr* den, uint32_t* zflag, hipStream_t st) {
     hipLaunchKernelGGL(k_lookup_rows, dim3(nblocks(n, 256)), dim3(256), 0, st, a, na, b, nt, nbc, afil, bfil, n, alpha,
-                       delta, out, ostride, comb, den);
+                       delta, out, ostride, comb, den, zflag);
     return hipGetLastError();
 }
 

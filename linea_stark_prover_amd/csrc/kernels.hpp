@@ -132,15 +132,15 @@ hipError_t launch_merkle_levels(Fr* layers, size_t nleaves, size_t stop_len, con
                                 size_t* off_out, size_t* len_out, hipStream_t st);
 
 // --------------------------------------------------------- k_field.hip
-// out[i] = 1 / in[i] (Montgomery trick, interleaved chunks); in may alias out? no
-// out[i] = 1/in[i] (0 -> 0); out != in.  scratch: batch_inverse_scratch(n)
-// elements (hierarchical, one Fermat inverse per call), or nullptr for the
-// single-level kernel (one inverse per 8..256 elements)
+// out[i] = 1/in[i] (0 -> 0: a zero input leaves the other outputs as they
+// are); out != in.  Montgomery's trick over workgroup product trees, one
+// Fermat inverse per call.  scratch: batch_inverse_scratch(n) elements (none
+// are read for n <= 4096)
 size_t batch_inverse_scratch(size_t n);
 // inv_total (optional, host value): 1/(product of all n inputs), when the caller
-// knows it in closed form -- the hierarchical path then skips its one Fermat
-// inversion (used only with a scratch buffer / n <= BI_BASE)
-hipError_t launch_batch_inverse(const Fr* in, Fr* out, size_t n, hipStream_t st, Fr* scratch = nullptr,
+// knows it in closed form and knows that no input is zero -- the one Fermat
+// inversion is then skipped
+hipError_t launch_batch_inverse(const Fr* in, Fr* out, size_t n, hipStream_t st, Fr* scratch,
                                 const Fr* inv_total = nullptr);
 // Fr-mul throughput probe: nthreads lanes x iters x 4 independent products
 hipError_t launch_calib_mul(Fr* out, size_t nthreads, uint32_t iters, hipStream_t st);
@@ -163,13 +163,15 @@ size_t witness_scratch_bytes(size_t n, uint32_t ntables);
 // hash values, b[c][i] = a[c][(mul i + add) mod n]; n a power of two, mul odd
 hipError_t launch_gen_raw_perm(uint64_t seed, size_t n, uint32_t ncols, uint64_t mul, uint64_t add, Fr* a, Fr* b,
                                hipStream_t st);
-// trace row i (stride ostride): a cols, b cols; al/bl = row combination + delta
+// trace row i (stride ostride): a cols, b cols; al/bl = row combination + delta.
+// *zflag (a device word the caller cleared) is set if some bl is 0
 hipError_t launch_perm_rows(const Fr* a, uint32_t na, const Fr* b, uint32_t nb, size_t n, Fr alpha, Fr delta,
-                            Fr* out, size_t ostride, Fr* al, Fr* bl, hipStream_t st);
-// trace row i: a cols, b tables, a_filter, b_filters; comb / den: (1 + nt) x n
+                            Fr* out, size_t ostride, Fr* al, Fr* bl, uint32_t* zflag, hipStream_t st);
+// trace row i: a cols, b tables, a_filter, b_filters; comb / den: (1 + nt) x n.
+// *zflag (a device word the caller cleared) is set if some den is 0
 hipError_t launch_lookup_rows(const Fr* a, uint32_t na, const Fr* b, uint32_t nt, uint32_t nbc, const Fr* afil,
                               const Fr* bfil, size_t n, Fr alpha, Fr delta, Fr* out, size_t ostride, Fr* comb,
-                              Fr* den, hipStream_t st);
+                              Fr* den, uint32_t* zflag, hipStream_t st);
 hipError_t launch_mul_vec(const Fr* x, const Fr* y, size_t n, Fr* out, hipStream_t st);
 hipError_t launch_put_col(const Fr* v, size_t n, Fr* out, size_t ostride, uint32_t col, hipStream_t st);
 // inclusive prefix product (product = true) or sum over Fr

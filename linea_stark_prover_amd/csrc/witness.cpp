@@ -63,6 +63,7 @@ void batch_inv(std::vector<Fr>& v) {
         pre[i] = acc;
         acc = fr_mul(acc, v[i]);
     }
+    LSP_REQUIRE(!fr_is_zero(acc), LSP_E_STATE, "tried to invert zero (row combination + delta = 0)");
     Fr inv = fr_inv(acc);
     for (size_t i = v.size(); i-- > 0;) {
         const Fr t = fr_mul(inv, pre[i]);
@@ -256,6 +257,24 @@ extern "C" int lsp_gen_wide_trace(uint64_t seed, uint32_t log_n, uint32_t nlooku
 
 // ------------------------------------------------- device witness (F1)
 namespace lsp {
+namespace {
+// The check column's last row and the zero-denominator flag come back in one
+// copy: the column's buffer has one element more than rows, and the row
+// kernels set that element's first word when a row combination + delta is 0.
+// The reference panics there (Field::inverse of zero); the batch inverse maps
+// 0 to 0, which would otherwise pass for a finished witness.
+uint32_t* clear_zero_flag(Fr* col, size_t n, hipStream_t st) {
+    LSP_HIP(hipMemsetAsync(col + n, 0, sizeof(Fr), st));
+    return reinterpret_cast<uint32_t*>(col + n);
+}
+Fr fetch_last_row(const Fr* col, size_t n, hipStream_t st) {
+    Fr tail[2];
+    LSP_HIP(hipMemcpyAsync(tail, col + n - 1, sizeof tail, hipMemcpyDeviceToHost, st));
+    LSP_HIP(hipStreamSynchronize(st));
+    LSP_REQUIRE(tail[1].v[0] == 0, LSP_E_STATE, "tried to invert zero (row combination + delta = 0)");
+    return tail[0];
+}
+}  // namespace
 // RawPermutationTrace::get_trace on the device: columns a.., b.., b_inverse,
 // check (prefix product of (a_comb + delta) / (b_comb + delta), must end at 1)
 void witness_permutation_device(lsp_ctx* ctx, const Fr* a, uint32_t na, const Fr* b, uint32_t nb, size_t n,
@@ -264,18 +283,17 @@ void witness_permutation_device(lsp_ctx* ctx, const Fr* a, uint32_t na, const Fr
     Fr* al = ctx->fbuf("wit_al", n);
     Fr* bl = ctx->fbuf("wit_bl", n);
     Fr* binv = ctx->fbuf("wit_binv", n);
-    Fr* chk = ctx->fbuf("wit_chk", n);
+    Fr* chk = ctx->fbuf("wit_chk", n + 1);
     const size_t sb = witness_scratch_bytes(n, 0);
     void* scratch = ctx->buf("wit_scratch", sb);
-    LSP_HIP(launch_perm_rows(a, na, b, nb, n, alpha, delta, out, ostride, al, bl, st));
+    uint32_t* zflag = clear_zero_flag(chk, n, st);
+    LSP_HIP(launch_perm_rows(a, na, b, nb, n, alpha, delta, out, ostride, al, bl, zflag, st));
     LSP_HIP(launch_batch_inverse(bl, binv, n, st, ctx->bi_scratch(n)));
     LSP_HIP(launch_mul_vec(al, binv, n, al, st));
     LSP_HIP(launch_fr_scan(al, chk, n, true, scratch, sb, st));
     LSP_HIP(launch_put_col(binv, n, out, ostride, na + nb, st));
     LSP_HIP(launch_put_col(chk, n, out, ostride, na + nb + 1, st));
-    Fr last;
-    LSP_HIP(hipMemcpyAsync(&last, chk + n - 1, sizeof(Fr), hipMemcpyDeviceToHost, st));
-    LSP_HIP(hipStreamSynchronize(st));
+    const Fr last = fetch_last_row(chk, n, st);
     LSP_REQUIRE(fr_eq(last, fr_one()), LSP_E_STATE,
                 "failed to check constrain: check column should be 1 on the last row");
 }
@@ -292,19 +310,18 @@ void witness_lookup_device(lsp_ctx* ctx, const Fr* a, uint32_t na, const Fr* b, 
     Fr* inv = ctx->fbuf("wit_inv", m);
     uint32_t* occ = (uint32_t*)ctx->buf("wit_occ", std::max<size_t>(1, n * nt) * sizeof(uint32_t));
     Fr* term = ctx->fbuf("wit_term", n);
-    Fr* psum = ctx->fbuf("wit_psum", n);
+    Fr* psum = ctx->fbuf("wit_psum", n + 1);
     const size_t sb = witness_scratch_bytes(n, nt);
     void* scratch = ctx->buf("wit_scratch", sb);
-    LSP_HIP(launch_lookup_rows(a, na, b, nt, nbc, afil, bfil, n, alpha, delta, out, ostride, comb, den, st));
+    uint32_t* zflag = clear_zero_flag(psum, n, st);
+    LSP_HIP(launch_lookup_rows(a, na, b, nt, nbc, afil, bfil, n, alpha, delta, out, ostride, comb, den, zflag, st));
     LSP_HIP(launch_batch_inverse(den, inv, m, st, ctx->bi_scratch(m)));
     LSP_HIP(launch_lookup_occurrences(comb, n, nt, afil, bfil, occ, scratch, sb, st));
     const uint32_t col_ainv = na + nt * nbc + 1 + nt;
     LSP_HIP(launch_lookup_terms(inv, occ, afil, n, nt, out, ostride, col_ainv, term, st));
     LSP_HIP(launch_fr_scan(term, psum, n, false, scratch, sb, st));
     LSP_HIP(launch_put_col(psum, n, out, ostride, col_ainv + 1 + 2 * nt, st));
-    Fr last;
-    LSP_HIP(hipMemcpyAsync(&last, psum + n - 1, sizeof(Fr), hipMemcpyDeviceToHost, st));
-    LSP_HIP(hipStreamSynchronize(st));
+    const Fr last = fetch_last_row(psum, n, st);
     LSP_REQUIRE(fr_is_zero(last), LSP_E_STATE, "failed to check constrain: check column should be 0 on the last row");
 }
 }  // namespace lsp
