@@ -24,7 +24,7 @@ std::string bounds_fault_report() {
     (void)hipDeviceSynchronize();  // the call's kernels are done (any stream)
     static const char* const files[] = {"k_ntt.hip", "k_hash.hip", "k_field.hip", "k_quotient.hip", "k_open.hip",
                                         "k_witness.hip", "k_check.hip", "fr29.hpp", "k_common.hpp", "poseidon2_f29.hpp",
-                                        "fr.hpp"};
+                                        "fr.hpp", "k_air_prog.hpp"};
     static unsigned (*const readers[])() = {bounds_fault_k_ntt, bounds_fault_k_hash, bounds_fault_k_field,
                                             bounds_fault_k_quotient, bounds_fault_k_open, bounds_fault_k_witness,
                                             bounds_fault_k_check};

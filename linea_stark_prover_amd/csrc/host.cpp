@@ -207,8 +207,8 @@ static void parse_program(Air& air, AirCfg& g, Next&& next, size_t cfg, bool pre
     LSP_REQUIRE(nconst >= 0 && nconst <= (1 << 16), LSP_E_ARG, where + ": more than 2^16 constants");
     LSP_REQUIRE(nops >= 1 && nops <= (1 << 20), LSP_E_ARG, where + ": op count outside [1, 2^20]");
     LSP_REQUIRE(nassert >= 1 && nassert <= nops, LSP_E_ARG, where + ": bad assert count");
-    g.nslots = (uint32_t)nslots;
-    g.nassert = (uint32_t)nassert;
+    air.has_prog = true;
+    air.prog_slots = std::max(air.prog_slots, (uint32_t)nslots);
     air.dev.insert(air.dev.end(), {LSP_AIR_PROGRAM, width, nslots, nconst, nops, nassert});
     for (int32_t i = 0; i < nconst; ++i) {
         Fr c;
@@ -283,59 +283,63 @@ static void parse_program(Air& air, AirCfg& g, Next&& next, size_t cfg, bool pre
 Air Air::parse(const int32_t* d, size_t n) {
     Air air;
     LSP_REQUIRE(d && n >= 1, LSP_E_ARG, "empty AIR descriptor");
+    LSP_REQUIRE(n <= (size_t)INT32_MAX, LSP_E_ARG, "AIR descriptor of 2^31 words or more");
     air.raw.assign(d, d + n);
-    size_t p = 0;
-    auto next = [&]() -> int32_t {
-        LSP_REQUIRE(p < n, LSP_E_ARG, "truncated AIR descriptor");
-        return d[p++];
+    // air_decode's reader over words nobody has checked yet
+    struct {
+        const int32_t* d;
+        size_t n, p;
+        int32_t word() {
+            LSP_REQUIRE(p < n, LSP_E_ARG, "truncated AIR descriptor");
+            return d[p++];
+        }
+        const int32_t* words(int64_t k) {
+            LSP_REQUIRE(k >= 0 && (uint64_t)k <= n - p, LSP_E_ARG, "truncated AIR descriptor");
+            p += (size_t)k;
+            return d + p - k;
+        }
+    } r{d, n, 0};
+    auto cols = [&](const int32_t* ids, int64_t k) {
+        for (int64_t i = 0; i < k; ++i) {
+            LSP_REQUIRE(ids[i] >= 0 && ids[i] < (1 << 20), LSP_E_ARG, "bad column id in AIR descriptor");
+            air.max_col = std::max(air.max_col, (uint32_t)ids[i]);
+        }
     };
-    auto col = [&]() -> int32_t {
-        int32_t c = next();
-        LSP_REQUIRE(c >= 0 && c < (1 << 20), LSP_E_ARG, "bad column id in AIR descriptor");
-        air.max_col = std::max(air.max_col, (uint32_t)c);
-        return c;
-    };
-    const int32_t nc = next();
+    auto count = [](int32_t k) { return k >= 1 && k <= 4096; };
+    const int32_t nc = r.word();
     LSP_REQUIRE(nc >= 1 && nc <= 4096, LSP_E_ARG, "bad config count in AIR descriptor");
     air.dev.push_back(nc);
     for (int32_t c = 0; c < nc; ++c) {
         AirCfg g;
-        const size_t p0 = p;
-        g.type = next();
-        if (g.type == LSP_AIR_PERMUTATION) {
-            const int32_t na = next(), nb = next();
-            LSP_REQUIRE(na >= 1 && nb >= 1 && na <= 4096 && nb <= 4096, LSP_E_ARG, "bad permutation widths");
-            for (int32_t i = 0; i < na; ++i) g.a.push_back(col());
-            for (int32_t i = 0; i < nb; ++i) g.b.push_back(col());
-            g.binv = col();
-            g.check = col();
-        } else if (g.type == LSP_AIR_LOOKUP) {
-            const int32_t na = next();
-            LSP_REQUIRE(na >= 1 && na <= 4096, LSP_E_ARG, "bad lookup A width");
-            for (int32_t i = 0; i < na; ++i) g.a.push_back(col());
-            g.ntab = next();
-            g.nbc = next();
-            LSP_REQUIRE(g.ntab >= 1 && g.nbc >= 1 && g.ntab <= 4096 && g.nbc <= 4096, LSP_E_ARG,
-                        "bad lookup B tables");
-            for (int32_t i = 0; i < g.ntab * g.nbc; ++i) g.b.push_back(col());
-            g.a_filter = col();
-            for (int32_t t = 0; t < g.ntab; ++t) g.b_filter.push_back(col());
-            g.a_inv = col();
-            for (int32_t t = 0; t < g.ntab; ++t) g.b_inv.push_back(col());
-            for (int32_t t = 0; t < g.ntab; ++t) g.occ.push_back(col());
-            g.check = col();
+        const size_t p0 = r.p;
+        g.type = r.word();
+        g.off = (int32_t)r.p;
+        if (g.type == LSP_AIR_PERMUTATION || g.type == LSP_AIR_LOOKUP) {
+            const AirView v = air_decode(g.type, r);
+            if (g.type == LSP_AIR_PERMUTATION) {
+                LSP_REQUIRE(count(v.na) && count(v.nbc), LSP_E_ARG, "bad permutation widths");
+            } else {
+                LSP_REQUIRE(count(v.na), LSP_E_ARG, "bad lookup A width");
+                LSP_REQUIRE(count(v.ntab) && count(v.nbc), LSP_E_ARG, "bad lookup B tables");
+                cols(&v.a_filter, 1);
+                cols(v.b_filter, v.ntab);
+                cols(&v.a_inv, 1);
+                cols(v.occ, v.ntab);
+            }
+            cols(v.a, v.na);
+            cols(v.b, (int64_t)v.ntab * v.nbc);
+            cols(v.b_inv, v.ntab);
+            cols(&v.check, 1);
+            air.dev.insert(air.dev.end(), d + p0, d + r.p);
         } else if (g.is_prog()) {
             // (appends its device form to air.dev)
-            parse_program(air, g, next, (size_t)c, g.type == LSP_AIR_PROGRAM_PREP);
-            air.has_prog = true;
-            air.prog_slots = std::max(air.prog_slots, g.nslots);
+            parse_program(air, g, [&] { return r.word(); }, (size_t)c, g.type == LSP_AIR_PROGRAM_PREP);
         } else {
             throw LspError(LSP_E_ARG, "unknown AIR config type");
         }
-        if (!g.is_prog()) air.dev.insert(air.dev.end(), d + p0, d + p);
         air.cfgs.push_back(std::move(g));
     }
-    LSP_REQUIRE(p == n, LSP_E_ARG, "trailing data in AIR descriptor");
+    LSP_REQUIRE(r.p == n, LSP_E_ARG, "trailing data in AIR descriptor");
     return air;
 }
 
@@ -350,85 +354,47 @@ void Air::require_fits(size_t w, size_t npub, size_t wp) const {
                 "AIR program reads public value " + std::to_string(max_pub) + " of " + std::to_string(npub));
 }
 
-// Symbolic degree_multiple rules of p3-uni-stark: main variables 1,
-// constants 0, public values `pd` (U6), IsFirstRow/IsLastRow 1,
-// IsTransition 0; Add/Sub max, Mul sum.  Horner combos start from ZERO.
-static int horner_deg(size_t n, int pd) {
-    int d = 0;
-    for (size_t i = 0; i < n; ++i) d = std::max(d + pd, 1);
-    return d;
+// Symbolic degree_multiple rules of p3-uni-stark as an algebra: main and
+// preprocessed variables 1, constants 0, public values `pd` (U6), IsFirstRow /
+// IsLastRow 1, IsTransition 0; Add / Sub max, Mul sum (saturating: 2^20
+// squarings would overflow, and any such degree is far past every blowup).
+namespace {
+struct DegAlgebra {
+    using V = int;
+    int zero() const { return 0; }
+    int one() const { return 0; }
+    int add(int a, int b) const { return std::max(a, b); }
+    int sub(int a, int b) const { return std::max(a, b); }
+    int mul(int a, int b) const { return (int)std::min<int64_t>((int64_t)a + b, 1 << 30); }
+    int load(const void*, int32_t) const { return 1; }
+};
+template <Sel S>
+constexpr int sel_degree(SelTag<S>) {
+    return S == Sel::First || S == Sel::Last ? 1 : 0;
 }
+}  // namespace
 
-// a program's asserts by the same rule, tracked slot by slot
-static void program_degrees(const AirCfg& g, int pd, std::vector<int>& out) {
-    int slot[AIR_PROG_MAX_SLOTS] = {0};
-    auto deg = [&](int32_t x) {
-        switch ((uint32_t)x >> 24) {
-            case AIR_OPND_SLOT: return slot[(uint32_t)x & 0xffffffu];
-            case AIR_OPND_LOCAL:
-            case AIR_OPND_NEXT:
-            case AIR_OPND_PREP_LOCAL:  // a preprocessed variable counts as a main one
-            case AIR_OPND_PREP_NEXT:
-            case AIR_OPND_FIRST:
-            case AIR_OPND_LAST: return 1;
-            case AIR_OPND_PUBLIC: return pd;
-            default: return 0;  // constants, IsTransition
-        }
+// walk(cfg index, degree of the constraint with its selector, what it is) over the whole AIR
+template <class F>
+static void walk_degrees(const Air& air, int pd, F&& f) {
+    const DegAlgebra D;
+    auto leaf = [&](const AirCfg&, uint32_t k, uint32_t) {
+        return k == AIR_OPND_PUBLIC ? pd : k == AIR_OPND_CONST || k == AIR_OPND_TRANS ? 0 : 1;
     };
-    for (size_t i = 0; i < g.pops.size(); i += 4) {
-        const int32_t* o = g.pops.data() + i;
-        if (o[0] == AIR_OP_ASSERT_ZERO) {
-            out.push_back(deg(o[2]));
-            continue;
-        }
-        const int a = deg(o[2]), b = deg(o[3]);
-        // (saturating: 2^20 squarings would overflow, and any such degree is far past every blowup)
-        slot[o[1]] = o[0] == AIR_OP_MUL ? std::min(a + b, 1 << 30) : std::max(a, b);
-    }
+    for (size_t c = 0; c < air.cfgs.size(); ++c)
+        air.walk(D, air.cfgs[c], nullptr, nullptr, pd, pd, leaf,
+                 [&](int v, auto sel, AirCons what) { f(c, D.mul(sel_degree(sel), v), what); });
 }
 
 std::vector<int> Air::degrees(int pd) const {
     std::vector<int> out;
-    for (const auto& g : cfgs) {
-        if (g.is_prog()) {
-            program_degrees(g, pd, out);
-        } else if (g.type == LSP_AIR_PERMUTATION) {
-            const int a = std::max(horner_deg(g.a.size(), pd), pd), b = std::max(horner_deg(g.b.size(), pd), pd);
-            out.insert(out.end(), {b + 1, 1 + std::max(1, a + 1), std::max(1, a + 2), 2});
-        } else {
-            const int a = std::max(horner_deg(g.a.size(), pd), pd);
-            const int bdeg = std::max(horner_deg((size_t)g.nbc, pd), pd);
-            out.push_back(a + 1);
-            for (int32_t t = 0; t < g.ntab; ++t) out.push_back(bdeg + 1);
-            out.insert(out.end(), {1 + 3, 3, 2});  // the LogUp sums are products of three columns
-        }
-    }
+    walk_degrees(*this, pd, [&](size_t, int deg, AirCons) { out.push_back(deg); });
     return out;
 }
 
 std::pair<int, int> Air::stats(int pd) const {
-    int maxd = 0, k = 0;
-    for (const auto& g : cfgs) {
-        if (g.is_prog()) {
-            std::vector<int> dg;
-            program_degrees(g, pd, dg);
-            for (int x : dg) maxd = std::max(maxd, x);
-            k += (int)g.nassert;
-        } else if (g.type == LSP_AIR_PERMUTATION) {
-            const int a = std::max(horner_deg(g.a.size(), pd), pd), b = std::max(horner_deg(g.b.size(), pd), pd);
-            maxd = std::max({maxd, b + 1, 1 + std::max(1, a + 1), std::max(1, a + 2), 2});
-            k += 4;
-        } else {
-            const int a = std::max(horner_deg(g.a.size(), pd), pd);
-            maxd = std::max(maxd, a + 1);
-            const int bdeg = std::max(horner_deg((size_t)g.nbc, pd), pd);
-            maxd = std::max(maxd, bdeg + 1);
-            const int lc = 3;
-            maxd = std::max({maxd, 1 + lc, lc, 2});
-            k += 1 + g.ntab + 3;
-        }
-    }
-    return {maxd, k};
+    const std::vector<int> d = degrees(pd);
+    return {d.empty() ? 0 : *std::max_element(d.begin(), d.end()), (int)d.size()};
 }
 
 uint32_t Air::log_quotient_degree(int pd) const {
@@ -444,35 +410,13 @@ void Air::eval_fold(const Fr* loc, const Fr* nxt, const Fr* pub, const Fr& first
 }
 
 Air::ConsInfo Air::constraint_info(uint32_t j) const {
+    ConsInfo o{};
     uint32_t k = 0;
-    for (size_t c = 0; c < cfgs.size(); ++c) {
-        const AirCfg& g = cfgs[c];
-        const uint32_t n = g.is_prog()                     ? g.nassert
-                           : g.type == LSP_AIR_PERMUTATION ? 4
-                                                           : 4 + (uint32_t)g.ntab;
-        if (j >= k + n) {
-            k += n;
-            continue;
-        }
-        const uint32_t i = j - k;
-        ConsInfo o{(uint32_t)c, g.type, 0, -1};
-        if (g.is_prog()) {
-            o.kind = LSP_CONSTRAINT_PROGRAM;
-        } else if (g.type == LSP_AIR_PERMUTATION) {
-            static const int32_t kinds[4] = {LSP_CONSTRAINT_B_INVERSE, LSP_CONSTRAINT_FIRST_ROW,
-                                             LSP_CONSTRAINT_TRANSITION, LSP_CONSTRAINT_LAST_ROW};
-            o.kind = kinds[i];
-        } else if (i == 0) {
-            o.kind = LSP_CONSTRAINT_A_INVERSE;
-        } else if (i <= (uint32_t)g.ntab) {
-            o.kind = LSP_CONSTRAINT_B_INVERSE;
-            o.table = (int32_t)(i - 1);
-        } else {
-            o.kind = LSP_CONSTRAINT_FIRST_ROW + (int32_t)(i - 1 - (uint32_t)g.ntab);
-        }
-        return o;
-    }
-    throw LspError(LSP_E_ARG, "constraint index past the AIR's last constraint");
+    walk_degrees(*this, 0, [&](size_t c, int, AirCons what) {
+        if (k++ == j) o = ConsInfo{(uint32_t)c, cfgs[c].type, what.kind, what.table};
+    });
+    LSP_REQUIRE(j < k, LSP_E_ARG, "constraint index past the AIR's last constraint");
+    return o;
 }
 
 }  // namespace lsp

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/lsp.h"
+#include "air_walk.hpp"
 #include "fr.hpp"
 #include "kernels.hpp"
 #include "poseidon2.hpp"
@@ -214,25 +215,12 @@ struct Challenger {
     }
 };
 
-// LSP_AIR_PROGRAM operands and opcodes (include/lsp.h)
-enum : uint32_t {
-    AIR_OPND_SLOT = 0, AIR_OPND_LOCAL = 1, AIR_OPND_NEXT = 2, AIR_OPND_PUBLIC = 3, AIR_OPND_CONST = 4,
-    AIR_OPND_FIRST = 5, AIR_OPND_LAST = 6, AIR_OPND_TRANS = 7,
-    // LSP_AIR_PROGRAM_PREP only: a cell of the preprocessed matrix
-    AIR_OPND_PREP_LOCAL = 8, AIR_OPND_PREP_NEXT = 9
-};
-enum : int32_t { AIR_OP_ADD = 1, AIR_OP_SUB = 2, AIR_OP_MUL = 3, AIR_OP_ASSERT_ZERO = 4 };
-constexpr uint32_t AIR_PROG_MAX_SLOTS = 16;
-
 struct AirCfg {
-    int type;  // 1 perm, 2 lookup, 3 program, 4 program that reads preprocessed columns
+    int type;  // LSP_AIR_*
     bool is_prog() const { return type == LSP_AIR_PROGRAM || type == LSP_AIR_PROGRAM_PREP; }
-    std::vector<int32_t> a, b;             // perm: a, b ; lookup: a, flattened b tables
-    int32_t binv = 0, check = 0;           // perm
-    int32_t ntab = 0, nbc = 0, a_filter = 0, a_inv = 0;
-    std::vector<int32_t> b_filter, b_inv, occ;
+    // a built-in: where its words follow its type word in Air::raw (air_decode reads them)
+    int32_t off = 0;
     // program: its constants (Montgomery form) and ops as [opcode, dst, a, b]
-    uint32_t nslots = 0, nassert = 0;
     std::vector<Fr> pconst;
     std::vector<int32_t> pops;
 };
@@ -257,6 +245,16 @@ struct Air {
     // and the preprocessed matrix is at least prep_width wide (wp = 0: the
     // call has none, so an AIR that reads one is refused)
     void require_fits(size_t w, size_t npub, size_t wp = 0) const;
+    // LineaAIR::eval of config g over an algebra A (air_walk.hpp): eval,
+    // degrees, stats and constraint_info below are all this walk.
+    // push(value, selector, what) per constraint in eval's order, the value
+    // not multiplied by its selector.  A built-in config is air_walk; a
+    // program's asserts come as they stand, under Sel::Always (a program takes
+    // the selectors as operands).  leaf(g, kind, payload): the value of a
+    // program operand other than a slot.
+    template <class A, class Row, class Leaf, class Push>
+    void walk(const A& F, const AirCfg& g, Row loc, Row nxt, const typename A::V& alpha,
+              const typename A::V& delta, Leaf&& leaf, Push&& push) const;
     // every constraint's degree under the U6 public-degree rule, in eval's order
     std::vector<int> degrees(int public_degree) const;
     // (max constraint degree, constraint count) under the U6 public-degree rule
@@ -282,68 +280,65 @@ struct Air {
     ConsInfo constraint_info(uint32_t j) const;
 };
 
-inline Fr air_horner(const Fr* row, const int32_t* ids, size_t n, const Fr& a) {
-    Fr acc = fr_zero();
-    for (size_t i = 0; i < n; ++i) acc = fr_add(fr_mul(acc, a), row[ids[i]]);
-    return acc;
+template <class A, class Row, class Leaf, class Push>
+void Air::walk(const A& F, const AirCfg& g, Row loc, Row nxt, const typename A::V& alpha, const typename A::V& delta,
+               Leaf&& leaf, Push&& push) const {
+    if (!g.is_prog()) {
+        AirWords r{raw.data(), g.off};
+        air_walk(F, g.type, r, loc, nxt, alpha, delta, push);
+        return;
+    }
+    typename A::V slot[AIR_PROG_MAX_SLOTS] = {};  // (parse: read only after an earlier op wrote it)
+    auto opnd = [&](int32_t x) -> typename A::V {
+        const uint32_t k = (uint32_t)x >> 24, v = (uint32_t)x & 0xffffffu;
+        return k == AIR_OPND_SLOT ? slot[v] : leaf(g, k, v);
+    };
+    for (size_t i = 0; i < g.pops.size(); i += 4) {
+        const int32_t* o = g.pops.data() + i;
+        if (o[0] == AIR_OP_ASSERT_ZERO) {
+            push(opnd(o[2]), SelTag<Sel::Always>{}, AirCons{LSP_CONSTRAINT_PROGRAM, -1});
+            continue;
+        }
+        const typename A::V x = opnd(o[2]), y = opnd(o[3]);
+        slot[o[1]] = o[0] == AIR_OP_ADD ? F.add(x, y) : o[0] == AIR_OP_SUB ? F.sub(x, y) : F.mul(x, y);
+    }
 }
+
+// the field itself, on rows of cells
+struct FrAlgebra {
+    using V = Fr;
+    Fr zero() const { return fr_zero(); }
+    Fr one() const { return fr_one(); }
+    Fr add(const Fr& a, const Fr& b) const { return fr_add(a, b); }
+    Fr sub(const Fr& a, const Fr& b) const { return fr_sub(a, b); }
+    Fr mul(const Fr& a, const Fr& b) const { return fr_mul(a, b); }
+    Fr load(const Fr* row, int32_t k) const { return row[k]; }
+};
 
 template <class Push>
 void Air::eval(const Fr* loc, const Fr* nxt, const Fr* pub, const Fr& first, const Fr& last, const Fr& trans,
                Push&& push, const Fr* ploc, const Fr* pnxt) const {
-    const Fr one = fr_one();
-    const Fr &ap = pub[0], &dl = pub[1];
-    for (const auto& g : cfgs) {
-        if (g.is_prog()) {
-            Fr slot[AIR_PROG_MAX_SLOTS];
-            auto opnd = [&](int32_t x) -> Fr {
-                const uint32_t k = (uint32_t)x >> 24, v = (uint32_t)x & 0xffffffu;
-                switch (k) {
-                    case AIR_OPND_SLOT: return slot[v];
-                    case AIR_OPND_LOCAL: return loc[v];
-                    case AIR_OPND_NEXT: return nxt[v];
-                    case AIR_OPND_PUBLIC: return pub[v];
-                    case AIR_OPND_CONST: return g.pconst[v];
-                    case AIR_OPND_FIRST: return first;
-                    case AIR_OPND_LAST: return last;
-                    case AIR_OPND_PREP_LOCAL: return ploc[v];
-                    case AIR_OPND_PREP_NEXT: return pnxt[v];
-                    default: return trans;
-                }
-            };
-            for (size_t i = 0; i < g.pops.size(); i += 4) {
-                const int32_t* o = g.pops.data() + i;
-                if (o[0] == AIR_OP_ASSERT_ZERO) {
-                    push(opnd(o[2]));
-                    continue;
-                }
-                const Fr x = opnd(o[2]), y = opnd(o[3]);
-                slot[o[1]] = o[0] == AIR_OP_ADD ? fr_add(x, y) : o[0] == AIR_OP_SUB ? fr_sub(x, y) : fr_mul(x, y);
-            }
-        } else if (g.type == LSP_AIR_PERMUTATION) {
-            const Fr a_l = fr_add(air_horner(loc, g.a.data(), g.a.size(), ap), dl);
-            const Fr b_l = fr_add(air_horner(loc, g.b.data(), g.b.size(), ap), dl);
-            push(fr_sub(fr_mul(b_l, loc[g.binv]), one));
-            push(fr_mul(first, fr_sub(loc[g.check], fr_mul(a_l, loc[g.binv]))));
-            const Fr a_n = fr_add(air_horner(nxt, g.a.data(), g.a.size(), ap), dl);
-            push(fr_mul(trans, fr_sub(nxt[g.check], fr_mul(fr_mul(loc[g.check], a_n), nxt[g.binv]))));
-            push(fr_mul(last, fr_sub(loc[g.check], one)));
-        } else {
-            const Fr a_l = fr_add(air_horner(loc, g.a.data(), g.a.size(), ap), dl);
-            push(fr_sub(fr_mul(a_l, loc[g.a_inv]), one));
-            Fr lc = fr_mul(loc[g.a_filter], loc[g.a_inv]);
-            Fr nc = fr_mul(nxt[g.a_filter], nxt[g.a_inv]);
-            for (int32_t t = 0; t < g.ntab; ++t) {
-                const Fr b_l = fr_add(air_horner(loc, g.b.data() + t * g.nbc, g.nbc, ap), dl);
-                push(fr_sub(fr_mul(b_l, loc[g.b_inv[t]]), one));
-                lc = fr_sub(lc, fr_mul(fr_mul(loc[g.b_filter[t]], loc[g.occ[t]]), loc[g.b_inv[t]]));
-                nc = fr_sub(nc, fr_mul(fr_mul(nxt[g.b_filter[t]], nxt[g.occ[t]]), nxt[g.b_inv[t]]));
-            }
-            push(fr_mul(first, fr_sub(loc[g.check], lc)));
-            push(fr_mul(trans, fr_sub(fr_sub(nxt[g.check], loc[g.check]), nc)));
-            push(fr_mul(last, loc[g.check]));
+    auto leaf = [&](const AirCfg& g, uint32_t k, uint32_t v) -> Fr {
+        switch (k) {
+            case AIR_OPND_LOCAL: return loc[v];
+            case AIR_OPND_NEXT: return nxt[v];
+            case AIR_OPND_PUBLIC: return pub[v];
+            case AIR_OPND_CONST: return g.pconst[v];
+            case AIR_OPND_FIRST: return first;
+            case AIR_OPND_LAST: return last;
+            case AIR_OPND_PREP_LOCAL: return ploc[v];
+            case AIR_OPND_PREP_NEXT: return pnxt[v];
+            default: return trans;
         }
-    }
+    };
+    for (const auto& g : cfgs)
+        walk(FrAlgebra{}, g, loc, nxt, pub[0], pub[1], leaf, [&](const Fr& x, auto sel, AirCons) {
+            constexpr Sel s = decltype(sel)::value;
+            if constexpr (s == Sel::Always)
+                push(x);
+            else
+                push(fr_mul(s == Sel::First ? first : s == Sel::Trans ? trans : last, x));
+        });
 }
 
 struct lsp_query {

@@ -24,7 +24,7 @@
 // executes every op (k_check's ballots rely on it) and the descriptor reads
 // are scalar loads.
 //
-// Bounds of the arithmetic (Q29 of the two kernels, fr29.hpp).  An operand is
+// Bounds of the arithmetic (Q29 below, fr29.hpp).  An operand is
 //   a loaded cell or public value   f29_from_fr: normalised, < 2 r (a cell of
 //                                   the trace or of the preprocessed matrix)
 //   a constant                      canonical: normalised, < r
@@ -39,10 +39,36 @@
 // inputs < 20 r.  The op set is closed: whatever a program computes, no op
 // sees a value outside what it accepts (tests/test_air_program.py models it).
 #pragma once
+#include "air_walk.hpp"
 #include "fr29.hpp"
 #include "k_common.hpp"
 
 namespace lsp {
+
+// The algebra the kernels walk an AIR over (air_walk.hpp), on the 29-bit-limb
+// product (fr29.hpp; ~2x the 8 x 32-bit product's rate): every trace value and
+// constant enters in the 29-bit form (x 2^261: a repack and a cheap reduction
+// from the ark form), sums and differences leave through the LDS-table
+// reduction (< 2 r, normalised), products stay as the multiplier leaves them
+// (normalised, < 8.92 r for inputs < 20 r).  Bounds: add / sub inputs < 20 r
+// give < 40 r with limbs < 1.5 2^30 (f29_reduce_qt takes < 64 r, limbs
+// < 2.41 2^30); f29_sub16 takes a subtrahend < 16 r.
+struct Q29 {
+    using V = F29;
+    const uint4* qt;  // f29_reduce_qt's table
+    uint32_t w;       // row width
+    __device__ __forceinline__ F29 zero() const { return f29_zero(); }
+    __device__ __forceinline__ F29 one() const { return f29_from_fr(fr_one()); }
+    __device__ __forceinline__ F29 add(const F29& a, const F29& b) const { return f29_reduce_qt(f29_lazy2(a, b), qt); }
+    __device__ __forceinline__ F29 sub(const F29& a, const F29& b) const { return f29_reduce_qt(f29_sub16(a, b), qt); }
+    __device__ __forceinline__ F29 mul(const F29& a, const F29& b) const { return f29_mul(a, b); }
+    // column k of a row (the host checks the descriptor's ids against the
+    // width before any launch, Air::require_fits; the debug build checks them
+    // again here)
+    __device__ __forceinline__ F29 load(const Fr* __restrict__ row, int32_t k) const {
+        return LSP_BOUNDS(k >= 0 && (uint32_t)k < w) ? f29_from_fr(row[k]) : f29_zero();
+    }
+};
 
 // what one thread evaluates a program on
 struct ProgEnv {
@@ -81,11 +107,11 @@ __device__ __forceinline__ F29 prog_operand(const ProgEnv& e, const int32_t* __r
                                             int32_t x) {
     const uint32_t kind = (uint32_t)x >> 24, v = (uint32_t)x & 0xffffffu;
     switch (kind) {
-        case 0: return prog_slot_ld(e, v);
-        case 1: return LSP_BOUNDS(v < e.w) ? f29_from_fr(e.loc[v]) : f29_zero();
-        case 2: return LSP_BOUNDS(v < e.w) ? f29_from_fr(e.nxt[v]) : f29_zero();
-        case 3: return LSP_BOUNDS(v < e.npub) ? f29_from_fr(e.pub[v]) : f29_zero();
-        case 4: {
+        case AIR_OPND_SLOT: return prog_slot_ld(e, v);
+        case AIR_OPND_LOCAL: return LSP_BOUNDS(v < e.w) ? f29_from_fr(e.loc[v]) : f29_zero();
+        case AIR_OPND_NEXT: return LSP_BOUNDS(v < e.w) ? f29_from_fr(e.nxt[v]) : f29_zero();
+        case AIR_OPND_PUBLIC: return LSP_BOUNDS(v < e.npub) ? f29_from_fr(e.pub[v]) : f29_zero();
+        case AIR_OPND_CONST: {
             F29 c = f29_zero();
             if (LSP_BOUNDS(v < nconst)) {
 #pragma unroll
@@ -93,11 +119,11 @@ __device__ __forceinline__ F29 prog_operand(const ProgEnv& e, const int32_t* __r
             }
             return c;
         }
-        case 5: return e.first;
-        case 6: return e.last;
-        case 8: return LSP_BOUNDS(v < e.wp) ? f29_from_fr(e.ploc[v]) : f29_zero();
-        case 9: return LSP_BOUNDS(v < e.wp) ? f29_from_fr(e.pnxt[v]) : f29_zero();
-        default: return e.trans;
+        case AIR_OPND_FIRST: return e.first;
+        case AIR_OPND_LAST: return e.last;
+        case AIR_OPND_PREP_LOCAL: return LSP_BOUNDS(v < e.wp) ? f29_from_fr(e.ploc[v]) : f29_zero();
+        case AIR_OPND_PREP_NEXT: return LSP_BOUNDS(v < e.wp) ? f29_from_fr(e.pnxt[v]) : f29_zero();
+        default: return e.trans;  // AIR_OPND_TRANS
     }
 }
 
@@ -113,12 +139,13 @@ __device__ __forceinline__ int32_t air_prog_run(const Q& F, const ProgEnv& e, co
     for (uint32_t i = 0; i < nops; ++i, op += 4) {
         const int32_t code = op[0];
         const F29 x = prog_operand(e, cst, nconst, op[2]);
-        if (code == 4) {
+        if (code == AIR_OP_ASSERT_ZERO) {
             on_assert(x);
             continue;
         }
         const F29 y = prog_operand(e, cst, nconst, op[3]);
-        prog_slot_st(e, (uint32_t)op[1], code == 3 ? F.mul(x, y) : code == 1 ? F.add(x, y) : F.sub(x, y));
+        prog_slot_st(e, (uint32_t)op[1],
+                     code == AIR_OP_MUL ? F.mul(x, y) : code == AIR_OP_ADD ? F.add(x, y) : F.sub(x, y));
     }
     return p + 5 + (int32_t)(nconst * 9 + nops * 4);
 }

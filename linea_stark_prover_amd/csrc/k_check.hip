@@ -33,34 +33,9 @@
 namespace lsp {
 
 namespace {
-// the 29-bit-limb arithmetic of k_quotient.hip's Q29, at the same bounds: add /
-// sub inputs < 20 r give < 40 r with limbs < 1.5 2^30 (f29_reduce_qt takes
-// < 64 r, limbs < 2.41 2^30) and leave normalised and < 2 r; f29_sub16 takes a
-// subtrahend < 16 r; products (< 8.92 r for inputs < 20 r) stay as the
-// multiplier leaves them
-struct Q29 {
-    const uint4* qt;
-    __device__ __forceinline__ F29 add(const F29& a, const F29& b) const { return f29_reduce_qt(f29_lazy2(a, b), qt); }
-    __device__ __forceinline__ F29 sub(const F29& a, const F29& b) const { return f29_reduce_qt(f29_sub16(a, b), qt); }
-    __device__ __forceinline__ F29 mul(const F29& a, const F29& b) const { return f29_mul(a, b); }
-};
-
-// column k of a row (lsp_check_constraints checks the descriptor's ids against
-// the width before any launch; the debug build checks them again here)
-__device__ __forceinline__ F29 ld29(const Fr* __restrict__ row, int32_t k, uint32_t w) {
-    return LSP_BOUNDS(k >= 0 && (uint32_t)k < w) ? f29_from_fr(row[k]) : f29_zero();
-}
-
-__device__ __forceinline__ F29 horner(const Q29& F, const Fr* __restrict__ row, const int32_t* __restrict__ ids,
-                                      int32_t n, const F29& a, uint32_t w) {
-    F29 acc = f29_zero();
-    for (int32_t k = 0; k < n; ++k) acc = F.add(F.mul(acc, a), ld29(row, ids[k], w));
-    return acc;
-}
-
 // v == 0 (mod r), exactly.  Bound: every value check_walk hands out is either
 // the result of Q29::sub (f29_reduce_qt: normalised limbs, value < 2 r) or a
-// loaded cell (ld29 -> f29_reduce: limbs 0..7 masked to 29 bits, value < 2 r
+// loaded cell (Q29::load -> f29_reduce: limbs 0..7 masked to 29 bits, value < 2 r
 // for any word below 2^256).  A normalised limb vector is the unique one of
 // its integer, and the only multiples of r in [0, 2 r) are 0 and r: the value
 // is zero mod r iff its limbs are all zero or are r's own limbs.  (The factor
@@ -77,8 +52,9 @@ __device__ __forceinline__ bool f29_is_zero_mod_r(const F29& v) {
 }
 
 // LineaAIR::eval on one row pair: push(value, selector) per constraint in
-// eval's order, value normalised and < 2 r, not multiplied by the selector.
-// i, in: the rows `loc` and `nxt` are (a program reads the preprocessed matrix
+// eval's order, value normalised and < 2 r, not multiplied by the selector
+// (the built-in configs: air_walk over Q29, the selector tag turned into the
+// row's 0/1).  i, in: the rows `loc` and `nxt` are (a program reads the preprocessed matrix
 // at the same two).
 // PROG: also run LSP_AIR_PROGRAM configs (k_air_prog.hpp; an instantiation of
 // its own, as in k_quotient.hip).  A program takes the 0/1 selectors as data
@@ -89,64 +65,20 @@ template <bool PROG, class Push>
 __device__ __forceinline__ void check_walk(const Q29& F, const CheckArgs& a, const Fr* __restrict__ loc,
                                            const Fr* __restrict__ nxt, uint64_t i, uint64_t in, bool first, bool last,
                                            Push&& push) {
-    const bool trans = !last, always = true;
-    const F29 one = f29_from_fr(fr_one());
+    const bool trans = !last;
     const F29 ap = f29_from_fr(a.pub_alpha), dl = f29_from_fr(a.pub_delta);
-    const int32_t* d = a.air;
-    int32_t p = 0;
-    const int32_t ncfg = d[p++];
+    AirWords d{a.air, 0};
+    const int32_t ncfg = d.word();
     for (int32_t c = 0; c < ncfg; ++c) {
-        const int32_t type = d[p++];
-        if (type == 1) {  // AirPermutationConfig: air/src/lib.rs:116-167
-            const int32_t na = d[p++], nb = d[p++];
-            const int32_t* aid = d + p;
-            p += na;
-            const int32_t* bid = d + p;
-            p += nb;
-            const int32_t binv = d[p++], chk = d[p++];
-            const F29 a_l = F.add(horner(F, loc, aid, na, ap, a.w), dl);
-            const F29 b_l = F.add(horner(F, loc, bid, nb, ap, a.w), dl);
-            const F29 lbinv = ld29(loc, binv, a.w), lchk = ld29(loc, chk, a.w);
-            push(F.sub(F.mul(b_l, lbinv), one), always);
-            push(F.sub(lchk, F.mul(a_l, lbinv)), first);
-            const F29 a_n = F.add(horner(F, nxt, aid, na, ap, a.w), dl);
-            push(F.sub(ld29(nxt, chk, a.w), F.mul(F.mul(lchk, a_n), ld29(nxt, binv, a.w))), trans);
-            push(F.sub(lchk, one), last);
-        } else if (!PROG || type == 2) {  // AirLookupConfig: air/src/lib.rs:57-114
-            const int32_t na = d[p++];
-            const int32_t* aid = d + p;
-            p += na;
-            const int32_t nt = d[p++], nbc = d[p++];
-            const int32_t* bid = d + p;
-            p += nt * nbc;
-            const int32_t afil = d[p++];
-            const int32_t* bfil = d + p;
-            p += nt;
-            const int32_t ainv = d[p++];
-            const int32_t* binv = d + p;
-            p += nt;
-            const int32_t* occ = d + p;
-            p += nt;
-            const int32_t chk = d[p++];
-            const F29 a_l = F.add(horner(F, loc, aid, na, ap, a.w), dl);
-            const F29 lainv = ld29(loc, ainv, a.w);
-            push(F.sub(F.mul(a_l, lainv), one), always);
-            F29 lc = F.mul(ld29(loc, afil, a.w), lainv);
-            F29 nc = F.mul(ld29(nxt, afil, a.w), ld29(nxt, ainv, a.w));
-            for (int32_t t = 0; t < nt; ++t) {
-                const F29 b_l = F.add(horner(F, loc, bid + t * nbc, nbc, ap, a.w), dl);
-                const F29 lbinv = ld29(loc, binv[t], a.w);
-                push(F.sub(F.mul(b_l, lbinv), one), always);
-                lc = F.sub(lc, F.mul(F.mul(ld29(loc, bfil[t], a.w), ld29(loc, occ[t], a.w)), lbinv));
-                nc = F.sub(nc, F.mul(F.mul(ld29(nxt, bfil[t], a.w), ld29(nxt, occ[t], a.w)), ld29(nxt, binv[t], a.w)));
-            }
-            const F29 lchk = ld29(loc, chk, a.w);
-            push(F.sub(lchk, lc), first);
-            push(F.sub(F.sub(ld29(nxt, chk, a.w), lchk), nc), trans);
-            push(lchk, last);
+        const int32_t type = d.word();
+        if (!PROG || type != LSP_AIR_PROGRAM) {
+            air_walk(F, type, d, loc, nxt, ap, dl, [&](const F29& v, auto sel, AirCons) {
+                constexpr Sel s = decltype(sel)::value;
+                push(v, s == Sel::Always || (s == Sel::First ? first : s == Sel::Trans ? trans : last));
+            });
         } else if constexpr (PROG) {
             extern __shared__ uint32_t prog_regs[];
-            const F29 zero = f29_zero();
+            const F29 zero = f29_zero(), one = F.one();
             const ProgEnv e{loc,
                             nxt,
                             a.w,
@@ -160,7 +92,7 @@ __device__ __forceinline__ void check_walk(const Q29& F, const CheckArgs& a, con
                             a.prep + i * a.wp,  // (rows i and in of the h x wp matrix)
                             a.prep + in * a.wp,
                             a.wp};
-            p = air_prog_run(F, e, d, p, [&](const F29& v) { push(f29_reduce_qt(v, F.qt), always); });
+            d.p = air_prog_run(F, e, d.d, d.p, [&](const F29& v) { push(f29_reduce_qt(v, F.qt), true); });
         }
     }
 }
@@ -170,7 +102,7 @@ __global__ __launch_bounds__(256) void k_check(CheckArgs a) {
     __shared__ uint4 qt[3 * F29_QTAB_N];  // f29_reduce_qt's table
     f29_qtab_init(qt);
     __syncthreads();
-    const Q29 F{qt};
+    const Q29 F{qt, a.w};
     const uint64_t t = gtid();
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t row0 = t - lane;  // the wave's first row
@@ -205,7 +137,7 @@ __global__ __launch_bounds__(64) void k_check_rows(CheckArgs a) {
     __shared__ uint4 qt[3 * F29_QTAB_N];
     f29_qtab_init(qt);
     __syncthreads();
-    const Q29 F{qt};
+    const Q29 F{qt, a.w};
     const uint64_t t = gtid();
     bool live = t < a.nrows;
     uint64_t i = live ? a.rows[t] : 0;
@@ -230,14 +162,7 @@ hipError_t launch_check(const CheckArgs& a, hipStream_t st) {
     if (a.prog) {
         if (!a.pub || a.npub < 2 || a.prog_slots > 16) return hipErrorInvalidValue;
         const uint32_t bs = air_prog_block(a.prog_slots);
-        const size_t lds = air_prog_lds_bytes(a.prog_slots, bs);
-        if (lds > 48 * 1024) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_check<true>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(k_check<true>, dim3(nblocks(a.h, bs)), dim3(bs), lds, st, a);
-        return hipGetLastError();
+        return launch_lds(k_check<true>, nblocks(a.h, bs), bs, air_prog_lds_bytes(a.prog_slots, bs), st, a);
     }
     hipLaunchKernelGGL(k_check<false>, dim3(nblocks(a.h, 256)), dim3(256), 0, st, a);
     return hipGetLastError();

@@ -24,4 +24,18 @@ __device__ __forceinline__ size_t gtid() { return (size_t)blockIdx.x * blockDim.
 
 inline unsigned nblocks(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
 
+// Launch a kernel with `lds` bytes of dynamic shared memory; more than 48 KB
+// of it is asked for by attribute first.
+template <class Args>
+inline hipError_t launch_lds(void (*kernel)(Args), unsigned blocks, unsigned bs, size_t lds, hipStream_t st,
+                             const Args& a) {
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(bs), lds, st, a);
+    return hipGetLastError();
+}
+
 }  // namespace lsp

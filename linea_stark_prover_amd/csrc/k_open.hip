@@ -318,13 +318,7 @@ hipError_t launch_reduce_prep(const PrepReduceArgs& a, hipStream_t st) {
     if (!a.prep || !a.wp || !a.inv_z || !a.inv_zn || !a.apw || !a.out || !reduce_prep_fits(a.wp, a.lds_max))
         return hipErrorInvalidValue;
     const size_t lds = 3 * F29_QTAB_N * sizeof(uint4) + (size_t)a.wp * sizeof(F29);
-    if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_reduce_prep),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_reduce_prep, dim3(nblocks(a.n, 256)), dim3(256), lds, st, a);
-    return hipGetLastError();
+    return launch_lds(k_reduce_prep, nblocks(a.n, 256), 256, lds, st, a);
 }
 
 hipError_t launch_reduce_matrix(const Fr* M, size_t n, uint32_t w, const Fr* apw, uint32_t npts, const Fr* inv,

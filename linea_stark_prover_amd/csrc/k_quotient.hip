@@ -8,6 +8,11 @@
 // constraint order of eval.  Row `local` is LDE row bitrev_Q(i) and `next`
 // is bitrev_Q((i + 2^log_q) mod Q) (get_evaluations_on_domain +
 // vertically_packed_row_pair).
+//
+// The built-in configs are air_walk (air_walk.hpp) over Q29 (k_air_prog.hpp),
+// at the bounds given there: a constraint under a selector is pushed as
+// selector * value, both factors < 20 r.  The quotient value leaves canonical
+// in the ark form.
 #include <cstdlib>
 
 #include "fr29.hpp"
@@ -18,35 +23,6 @@
 namespace lsp {
 
 namespace {
-// The constraint arithmetic runs on the 29-bit-limb product (fr29.hpp; ~2x the
-// 8 x 32-bit product's rate): every trace value and constant enters in the
-// 29-bit form (x 2^261: a repack and a cheap reduction from the ark form),
-// sums and differences leave through the LDS-table reduction (< 2 r,
-// normalised), products stay as the multiplier leaves them (normalised,
-// < 8.92 r for inputs < 20 r), and the quotient value leaves canonical in the
-// ark form.  Bounds: add / sub inputs < 20 r give < 40 r with limbs < 1.5 2^30
-// (f29_reduce_qt takes < 64 r, limbs < 2.41 2^30); f29_sub16 takes a
-// subtrahend < 16 r.
-struct Q29 {
-    const uint4* qt;
-    __device__ __forceinline__ F29 add(const F29& a, const F29& b) const { return f29_reduce_qt(f29_lazy2(a, b), qt); }
-    __device__ __forceinline__ F29 sub(const F29& a, const F29& b) const { return f29_reduce_qt(f29_sub16(a, b), qt); }
-    __device__ __forceinline__ F29 mul(const F29& a, const F29& b) const { return f29_mul(a, b); }
-};
-
-// column k of a row (the descriptor's ids are checked against the width on
-// the host, Air::parse; the debug build checks them again here)
-__device__ __forceinline__ F29 ld29(const Fr* __restrict__ row, int32_t k, uint32_t w) {
-    return LSP_BOUNDS(k >= 0 && (uint32_t)k < w) ? f29_from_fr(row[k]) : f29_zero();
-}
-
-__device__ __forceinline__ F29 horner(const Q29& F, const Fr* __restrict__ row, const int32_t* __restrict__ ids,
-                                      int32_t n, const F29& a, uint32_t w) {
-    F29 acc = f29_zero();
-    for (int32_t k = 0; k < n; ++k) acc = F.add(F.mul(acc, a), ld29(row, ids[k], w));
-    return acc;
-}
-
 __global__ __launch_bounds__(256) void k_selector_denoms(const Fr* __restrict__ tabQ, uint32_t L1, Fr gen,
                                                          Fr wh_inv, size_t n, uint64_t i0, uint32_t log_step,
                                                          Fr* __restrict__ den) {
@@ -74,12 +50,11 @@ __global__ __launch_bounds__(256) void k_quotient(QuotientArgs a) {
     __shared__ uint4 qt[3 * F29_QTAB_N];  // f29_reduce_qt's table
     f29_qtab_init(qt);
     __syncthreads();
-    const Q29 F{qt};
+    const Q29 F{qt, a.w};
     const size_t t = gtid();
     const size_t Q = 1ull << a.logQ;
     const size_t npts = a.n ? a.n : Q;
     if (t >= npts) return;  // n = Q >> log_step points
-    const size_t tcons = t;  // (the lookup loop below names its table index t)
     // Row order: thread t evaluates point m = bitrev(t), whose row bitrev_Q(i)
     // is row0 + t, so a wave reads 64 adjacent LDE rows (and their
     // successors).  In point order it read rows Q/64 apart: with the C3
@@ -91,7 +66,6 @@ __global__ __launch_bounds__(256) void k_quotient(QuotientArgs a) {
     const size_t m = a.row_order ? brev_bits(t, a.logQ - a.log_step) : t;
     const uint64_t i = a.i0 + ((uint64_t)m << a.log_step);
     const uint32_t qmask = (1u << a.log_q) - 1;
-    const F29 one = f29_from_fr(fr_one());
     const Fr x = fr_mul(a.gen, pow2l(a.tabQ, a.L1, i));
     const Fr xm1 = fr_sub(x, fr_one());
     const Fr xml = fr_sub(x, a.wh_inv);
@@ -113,63 +87,23 @@ __global__ __launch_bounds__(256) void k_quotient(QuotientArgs a) {
 #define PUSH(X)                                     \
     do {                                            \
         if constexpr (EARLY)                        \
-            st_cons(a, ncw++, tcons, npts, (X));    \
+            st_cons(a, ncw++, t, npts, (X));        \
         else                                        \
             acc = F.add(F.mul(acc, al), (X));       \
     } while (0)
-    const int32_t* d = a.air;
-    int32_t p = 0;
-    const int32_t ncfg = d[p++];
+    AirWords d{a.air, 0};
+    const int32_t ncfg = d.word();
     for (int32_t c = 0; c < ncfg; ++c) {
-        const int32_t type = d[p++];
-        if (type == 1) {  // AirPermutationConfig: air/src/lib.rs:116-167
-            const int32_t na = d[p++], nb = d[p++];
-            const int32_t* aid = d + p;
-            p += na;
-            const int32_t* bid = d + p;
-            p += nb;
-            const int32_t binv = d[p++], chk = d[p++];
-            const F29 a_l = F.add(horner(F, loc, aid, na, ap, a.w), dl);
-            const F29 b_l = F.add(horner(F, loc, bid, nb, ap, a.w), dl);
-            const F29 lbinv = ld29(loc, binv, a.w), lchk = ld29(loc, chk, a.w);
-            PUSH(F.sub(F.mul(b_l, lbinv), one));
-            PUSH(F.mul(first, F.sub(lchk, F.mul(a_l, lbinv))));
-            const F29 a_n = F.add(horner(F, nxt, aid, na, ap, a.w), dl);
-            PUSH(F.mul(trans, F.sub(ld29(nxt, chk, a.w), F.mul(F.mul(lchk, a_n), ld29(nxt, binv, a.w)))));
-            PUSH(F.mul(last, F.sub(lchk, one)));
-        } else if (!PROG || type == 2) {  // AirLookupConfig: air/src/lib.rs:57-114
-            const int32_t na = d[p++];
-            const int32_t* aid = d + p;
-            p += na;
-            const int32_t nt = d[p++], nbc = d[p++];
-            const int32_t* bid = d + p;
-            p += nt * nbc;
-            const int32_t afil = d[p++];
-            const int32_t* bfil = d + p;
-            p += nt;
-            const int32_t ainv = d[p++];
-            const int32_t* binv = d + p;
-            p += nt;
-            const int32_t* occ = d + p;
-            p += nt;
-            const int32_t chk = d[p++];
-            const F29 a_l = F.add(horner(F, loc, aid, na, ap, a.w), dl);
-            const F29 lainv = ld29(loc, ainv, a.w);
-            PUSH(F.sub(F.mul(a_l, lainv), one));
-            F29 lc = F.mul(ld29(loc, afil, a.w), lainv);
-            F29 nc = F.mul(ld29(nxt, afil, a.w), ld29(nxt, ainv, a.w));
-            for (int32_t t = 0; t < nt; ++t) {
-                const F29 b_l = F.add(horner(F, loc, bid + t * nbc, nbc, ap, a.w), dl);
-                const F29 lbinv = ld29(loc, binv[t], a.w);
-                PUSH(F.sub(F.mul(b_l, lbinv), one));
-                lc = F.sub(lc, F.mul(F.mul(ld29(loc, bfil[t], a.w), ld29(loc, occ[t], a.w)), lbinv));
-                nc = F.sub(nc, F.mul(F.mul(ld29(nxt, bfil[t], a.w), ld29(nxt, occ[t], a.w)), ld29(nxt, binv[t], a.w)));
-            }
-            const F29 lchk = ld29(loc, chk, a.w);
-            PUSH(F.mul(first, F.sub(lchk, lc)));
-            PUSH(F.mul(trans, F.sub(F.sub(ld29(nxt, chk, a.w), lchk), nc)));
-            PUSH(F.mul(last, lchk));
-        } else if constexpr (PROG) {  // LSP_AIR_PROGRAM: the selectors are operands, an assert's value is pushed as it stands
+        const int32_t type = d.word();
+        if (!PROG || type != LSP_AIR_PROGRAM) {
+            air_walk(F, type, d, loc, nxt, ap, dl, [&](const F29& v, auto sel, AirCons) {
+                constexpr Sel s = decltype(sel)::value;
+                if constexpr (s == Sel::Always)
+                    PUSH(v);
+                else
+                    PUSH(F.mul(s == Sel::First ? first : s == Sel::Trans ? trans : last, v));
+            });
+        } else if constexpr (PROG) {  // the selectors are operands, an assert's value is pushed as it stands
             extern __shared__ uint32_t prog_regs[];
             // the preprocessed matrix at the rows of `loc` and `nxt`
             const ProgEnv e{loc,        nxt,          a.w,
@@ -177,7 +111,7 @@ __global__ __launch_bounds__(256) void k_quotient(QuotientArgs a) {
                             last,       trans,        prog_regs,
                             a.prog_slots, a.prep + lrow * a.wp, a.prep + nrow * a.wp,
                             a.wp};
-            p = air_prog_run(F, e, d, p, [&](const F29& v) { PUSH(v); });
+            d.p = air_prog_run(F, e, d.d, d.p, [&](const F29& v) { PUSH(v); });
         }
     }
 #undef PUSH
@@ -190,7 +124,7 @@ __global__ __launch_bounds__(256) void k_quotient_fold(QuotientArgs a) {
     __shared__ uint4 qt[3 * F29_QTAB_N];
     f29_qtab_init(qt);
     __syncthreads();
-    const Q29 F{qt};
+    const Q29 F{qt, 0};  // (loads no row)
     const size_t t = gtid();
     const size_t npts = a.n ? a.n : (1ull << a.logQ);
     if (t >= npts) return;
@@ -233,22 +167,15 @@ static QuotientArgs with_order(const QuotientArgs& a) {
 }
 
 // The program-capable walker: its register file is dynamic shared memory sized
-// by the descriptor's largest nslots (k_air_prog.hpp); more than 48 KB of it
-// (6 slots and up at 256 threads) is asked for by attribute first.
+// by the descriptor's largest nslots (k_air_prog.hpp; above 48 KB from 6 slots
+// up at 256 threads, launch_lds).
 template <bool EARLY>
 static hipError_t launch_quotient_prog_t(const QuotientArgs& b, size_t n, hipStream_t st) {
     if (!b.pub || b.npub < 2 || b.prog_slots > 16) return hipErrorInvalidValue;
     // a preprocessed matrix is the whole LDE, indexed like `lde` from row 0
     if (b.wp && (!b.prep || b.row0 || b.lde_next)) return hipErrorInvalidValue;
     const uint32_t bs = air_prog_block(b.prog_slots);
-    const size_t lds = air_prog_lds_bytes(b.prog_slots, bs);
-    if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_quotient<EARLY, true>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((k_quotient<EARLY, true>), dim3(nblocks(n, bs)), dim3(bs), lds, st, b);
-    return hipGetLastError();
+    return launch_lds(k_quotient<EARLY, true>, nblocks(n, bs), bs, air_prog_lds_bytes(b.prog_slots, bs), st, b);
 }
 static hipError_t launch_quotient_prog(const QuotientArgs& b, size_t n, hipStream_t st) {
     return b.cons ? launch_quotient_prog_t<true>(b, n, st) : launch_quotient_prog_t<false>(b, n, st);
