@@ -261,6 +261,33 @@ int lsp_merkle_layer(const lsp_tree *tree, uint32_t level, lsp_fr *out);
 /* Mmcs::verify_batch (host) -- LSP_OK or LSP_E_VERIFY */
 int lsp_merkle_verify(const lsp_ctx *ctx, const lsp_fr *root, const size_t *widths, size_t nmats,
                       uint32_t log_height, size_t index, const lsp_fr *rows, const lsp_fr *path);
+/* MerkleTreeMmcs::commit over matrices of unequal heights (p3-merkle-tree's
+ * first_digest_layer / compress_and_inject).  Matrix
+ * j is heights[j] x widths[j], row-major; every height a power of two.  A
+ * class = the matrices of one height, in the caller's order; H = the tallest.
+ *   leaf i            = hash_iter(rows i of the class-H matrices, concatenated)
+ *   node i of a level = compress(left, right), and where a class has as many
+ *                       rows as the level has nodes,
+ *                       compress(compress(left, right), hash_iter(rows i of it))
+ * A class of one row is injected into the root; if H = 1 the root is the leaf.
+ * With one height this is lsp_merkle_commit, byte for byte.  Every level runs
+ * on the GPU.  Opening the tree at index < H gives row index >> log2(H /
+ * heights[j]) of every matrix, in the caller's order, and log2(H) digests;
+ * its layers are the 2H - 1 digests after injection.
+ * LSP_E_SIZE: a height that is no power of two or above 2^40, a matrix of
+ * more than 2^48 elements.  LSP_E_ARG: no matrix, a width outside [1, 2^20],
+ * more than 8 matrices of one height (any number of heights). */
+int lsp_merkle_commit_mixed(lsp_ctx *ctx, const lsp_fr *const *mats, const size_t *widths, const size_t *heights,
+                            size_t nmats, int mem, lsp_fr *root, lsp_tree **tree);
+/* Mmcs::verify_batch of such a batch (host; works on a host-only context):
+ * rows = one opened row per matrix in the caller's order, path = log2(H)
+ * digests.  LSP_OK or LSP_E_VERIFY; the argument errors of the commit, and
+ * LSP_E_ARG for index >= H. */
+int lsp_merkle_verify_mixed(const lsp_ctx *ctx, const lsp_fr *root, const size_t *widths, const size_t *heights,
+                            size_t nmats, size_t index, const lsp_fr *rows, const lsp_fr *path);
+/* Dimensions of a tree's matrices in the caller's order: up to cap entries of
+ * heights / widths (either may be NULL), *n (if given) = how many there are. */
+int lsp_tree_dims(const lsp_tree *tree, size_t *heights, size_t *widths, size_t cap, size_t *n);
 int lsp_tree_free(lsp_tree *tree);
 
 /* ----------------------------------------------------------- FriFolder */

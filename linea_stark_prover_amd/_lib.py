@@ -113,6 +113,16 @@ _SIGS = {
     "lsp_merkle_layer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, c_fr_p]),
     "lsp_merkle_verify": (ctypes.c_int, [ctypes.c_void_p, c_fr_p, ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
                                          ctypes.c_uint32, ctypes.c_size_t, c_fr_p, c_fr_p]),
+    "lsp_merkle_commit_mixed": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
+                                               ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
+                                               ctypes.c_size_t, ctypes.c_int, c_fr_p,
+                                               ctypes.POINTER(ctypes.c_void_p)]),
+    "lsp_merkle_verify_mixed": (ctypes.c_int, [ctypes.c_void_p, c_fr_p, ctypes.POINTER(ctypes.c_size_t),
+                                               ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t, ctypes.c_size_t,
+                                               c_fr_p, c_fr_p]),
+    "lsp_tree_dims": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t),
+                                     ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
+                                     ctypes.POINTER(ctypes.c_size_t)]),
     "lsp_tree_free": (ctypes.c_int, [ctypes.c_void_p]),
     "lsp_fri_fold": (ctypes.c_int, [ctypes.c_void_p, c_fr_p, ctypes.c_size_t, c_fr_p, c_fr_p, ctypes.c_int]),
     "lsp_fri_fold_row": (None, [ctypes.c_size_t, ctypes.c_uint32, c_fr_p, c_fr_p, c_fr_p, c_fr_p]),

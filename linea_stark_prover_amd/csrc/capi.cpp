@@ -23,13 +23,13 @@ std::string bounds_fault_report() {
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return "";
     (void)hipDeviceSynchronize();  // the call's kernels are done (any stream)
     static const char* const files[] = {"k_ntt.hip", "k_hash.hip", "k_field.hip", "k_quotient.hip", "k_open.hip",
-                                        "k_witness.hip", "k_check.hip", "fr29.hpp", "k_common.hpp", "poseidon2_f29.hpp",
-                                        "fr.hpp", "k_air_prog.hpp"};
+                                        "k_witness.hip", "k_check.hip", "k_merkle_inject.hip", "fr29.hpp", "k_common.hpp",
+                                        "poseidon2_f29.hpp", "fr.hpp", "k_air_prog.hpp"};
     static unsigned (*const readers[])() = {bounds_fault_k_ntt, bounds_fault_k_hash, bounds_fault_k_field,
                                             bounds_fault_k_quotient, bounds_fault_k_open, bounds_fault_k_witness,
-                                            bounds_fault_k_check};
+                                            bounds_fault_k_check, bounds_fault_k_merkle_inject};
     static const char* const tus[] = {"k_ntt.hip", "k_hash.hip", "k_field.hip", "k_quotient.hip", "k_open.hip",
-                                      "k_witness.hip", "k_check.hip"};
+                                      "k_witness.hip", "k_check.hip", "k_merkle_inject.hip"};
     std::string out;
     for (size_t t = 0; t < sizeof readers / sizeof readers[0]; ++t) {
         const unsigned v = readers[t]();
@@ -562,8 +562,8 @@ int lsp_merkle_open(const lsp_tree* t, size_t index, lsp_fr* rows_out, lsp_fr* p
         size_t o = 0;
         if (rows_out)
             for (size_t k = 0; k < t->mats.size(); ++k) {
-                LSP_HIP(hipMemcpy(rows_out + o, t->mats[k] + index * t->widths[k], t->widths[k] * sizeof(Fr),
-                                  hipMemcpyDeviceToHost));
+                LSP_HIP(hipMemcpy(rows_out + o, t->mats[k] + t->row_of(k, index) * t->widths[k],
+                                  t->widths[k] * sizeof(Fr), hipMemcpyDeviceToHost));
                 o += t->widths[k];
             }
         if (path_out) {
@@ -610,6 +610,73 @@ int lsp_merkle_verify(const lsp_ctx* ctx, const lsp_fr* root, const size_t* widt
         cur = ((index >> i) & 1) ? ctx->p2.compress(sib, cur) : ctx->p2.compress(cur, sib);
     }
     return fr_eq(cur, to_fr(*root)) ? LSP_OK : LSP_E_VERIFY;
+}
+
+int lsp_merkle_commit_mixed(lsp_ctx* ctx, const lsp_fr* const* mats, const size_t* widths, const size_t* heights,
+                            size_t nmats, int mem, lsp_fr* root, lsp_tree** tree) {
+    return guarded(ctx, [&] {
+        LSP_REQUIRE(ctx && mats && widths && heights && root, LSP_E_ARG, "bad merkle_commit_mixed arguments");
+        LSP_REQUIRE(mem == LSP_MEM_HOST || mem == LSP_MEM_DEVICE, LSP_E_ARG,
+                    "mem must be LSP_MEM_HOST or LSP_MEM_DEVICE");
+        const std::vector<HeightClass> cls = height_classes(widths, heights, nmats);
+        for (size_t k = 0; k < nmats; ++k) LSP_REQUIRE(mats[k], LSP_E_ARG, "null matrix");
+        std::lock_guard<std::mutex> g(ctx->mu);
+        need_gpu(ctx);
+        // the tree and its device memory, freed on every path out unless handed over
+        struct Owned {
+            lsp_tree* t = new lsp_tree();
+            ~Owned() {
+                if (!t) return;
+                for (auto* d : t->mats) (void)hipFree(d);
+                (void)hipFree(t->layers);
+                delete t;
+            }
+        } own;
+        lsp_tree* t = own.t;
+        t->ctx = ctx;
+        t->height = cls[0].height;
+        t->widths.assign(widths, widths + nmats);
+        t->heights.assign(heights, heights + nmats);
+        for (size_t k = 0; k < nmats; ++k) {
+            const size_t bytes = heights[k] * widths[k] * sizeof(Fr);
+            Fr* d = nullptr;
+            LSP_HIP(hipMalloc(&d, bytes));
+            t->mats.push_back(d);
+            LSP_HIP(hipMemcpyAsync(d, mats[k], bytes,
+                                   mem == LSP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                                   ctx->stream));
+        }
+        LSP_HIP(hipMalloc(&t->layers, (2 * t->height - 1) * sizeof(Fr)));
+        *root = from_fr(commit_mixed_device(ctx, cls, t->mats.data(), widths, t->layers));
+        if (tree) {
+            *tree = t;
+            own.t = nullptr;
+        }
+    });
+}
+
+int lsp_merkle_verify_mixed(const lsp_ctx* ctx, const lsp_fr* root, const size_t* widths, const size_t* heights,
+                            size_t nmats, size_t index, const lsp_fr* rows, const lsp_fr* path) {
+    bool ok = false;
+    const int rc = guarded(nullptr, [&] {
+        LSP_REQUIRE(ctx && root && widths && heights && rows, LSP_E_ARG, "bad merkle_verify_mixed arguments");
+        const std::vector<HeightClass> cls = height_classes(widths, heights, nmats);
+        LSP_REQUIRE(index < cls[0].height, LSP_E_ARG, "index out of range");
+        LSP_REQUIRE(path || cls[0].height == 1, LSP_E_ARG, "null path");
+        ok = verify_mixed_host(ctx, to_fr(*root), cls, widths, nmats, index, rows, path);
+    });
+    return rc != LSP_OK ? rc : ok ? LSP_OK : LSP_E_VERIFY;
+}
+
+int lsp_tree_dims(const lsp_tree* t, size_t* heights, size_t* widths, size_t cap, size_t* n) {
+    if (!t) return LSP_E_ARG;
+    const size_t nm = t->widths.size();
+    if (n) *n = nm;
+    for (size_t k = 0; k < nm && k < cap; ++k) {
+        if (heights) heights[k] = t->heights.empty() ? t->height : t->heights[k];
+        if (widths) widths[k] = t->widths[k];
+    }
+    return LSP_OK;
 }
 
 int lsp_tree_free(lsp_tree* t) {

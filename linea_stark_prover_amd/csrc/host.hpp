@@ -381,8 +381,16 @@ struct lsp_raw_trace {
 
 struct lsp_tree {
     lsp_ctx* ctx = nullptr;
-    size_t height = 0;
+    size_t height = 0;                 // of the tallest matrices = the number of leaves
     std::vector<size_t> widths;
+    std::vector<size_t> heights;       // per matrix (lsp_merkle_commit_mixed); empty: every matrix is `height` rows
+    // the row of matrix k that the opening at leaf `index` holds
+    size_t row_of(size_t k, size_t index) const {
+        size_t r = index;
+        if (!heights.empty())
+            for (size_t h = heights[k]; h < height; h <<= 1) r >>= 1;
+        return r;
+    }
     lsp::Fr* layers = nullptr;         // device, 2*height - 1
     std::vector<lsp::Fr*> mats;        // device copies (owned) of the committed matrices
 };

@@ -131,6 +131,13 @@ hipError_t launch_merkle_tree(Fr* layers, size_t nleaves, const F29* rc29, P2Lay
 hipError_t launch_merkle_levels(Fr* layers, size_t nleaves, size_t stop_len, const F29* rc29, P2Layout L,
                                 size_t* off_out, size_t* len_out, hipStream_t st);
 
+// --------------------------------------------------- k_merkle_inject.hip
+// dst[i] = compress(compress(src[2i], src[2i+1]), inj[i]) for i < nout: a level
+// of a mixed-height tree that takes in the row digests `inj` of the matrices
+// nout rows high (U14).  inj may be dst (overwritten in place); src may not
+hipError_t launch_merkle_inject(const Fr* src, const Fr* inj, Fr* dst, size_t nout, const F29* rc29, P2Layout L,
+                                hipStream_t st);
+
 // --------------------------------------------------------- k_field.hip
 // out[i] = 1/in[i] (0 -> 0: a zero input leaves the other outputs as they
 // are); out != in.  Montgomery's trick over workgroup product trees, one
@@ -350,6 +357,7 @@ unsigned bounds_fault_k_quotient();
 unsigned bounds_fault_k_open();
 unsigned bounds_fault_k_witness();
 unsigned bounds_fault_k_check();
+unsigned bounds_fault_k_merkle_inject();
 #endif
 // one matrix opened at npts points (the generic reduce of TwoAdicFriPcs::open):
 // ro[i] += sum_p (offys[p] - off[p] * sum_c apw[c] M[i][c]) * inv[p*n + i]

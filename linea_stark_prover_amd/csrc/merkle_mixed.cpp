@@ -1,0 +1,92 @@
+// MerkleTreeMmcs over matrices of unequal heights:
+// the tallest matrices make the leaves, every class of shorter ones is hashed
+// row by row and injected at the level with as many nodes as it has rows.
+// Every level runs on the GPU; commit_device (merkle.cpp), the prover's path,
+// is not involved.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "host.hpp"
+#include "prove_internal.hpp"
+
+namespace lsp {
+
+std::vector<HeightClass> height_classes(const size_t* widths, const size_t* heights, size_t nmats) {
+    LSP_REQUIRE(widths && heights && nmats >= 1, LSP_E_ARG, "a batch needs at least one matrix");
+    std::vector<size_t> order(nmats);
+    for (size_t k = 0; k < nmats; ++k) {
+        LSP_REQUIRE(widths[k] >= 1 && widths[k] <= ((size_t)1 << 20), LSP_E_ARG, "matrix width outside [1, 2^20]");
+        LSP_REQUIRE(heights[k] <= ((size_t)1 << 40), LSP_E_SIZE, "matrix height beyond 2^40");
+        log2_exact(heights[k]);
+        // (at most 2^60 here) so that no byte count below overflows
+        LSP_REQUIRE(heights[k] * widths[k] <= ((size_t)1 << 48), LSP_E_SIZE, "matrix beyond 2^48 elements");
+        order[k] = k;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return heights[a] > heights[b]; });
+    std::vector<HeightClass> cls;
+    for (size_t k : order) {
+        if (cls.empty() || cls.back().height != heights[k]) cls.push_back({heights[k], {}});
+        LSP_REQUIRE(cls.back().idx.size() < 8, LSP_E_ARG, "more than 8 matrices of one height");
+        cls.back().idx.push_back(k);
+    }
+    return cls;
+}
+
+Fr commit_mixed_device(lsp_ctx* ctx, const std::vector<HeightClass>& cls, const Fr* const* mats, const size_t* widths,
+                       Fr* layers) {
+    hipStream_t st = ctx->stream;
+    const size_t H = cls[0].height;
+    // every class's row digests, into the layer they enter: the leaves for the
+    // tallest class, for the others the layer the injecting level then
+    // overwrites in place.  The levels' dependent chain holds no sponge.
+    for (const HeightClass& c : cls) {
+        MatList m{};
+        m.n = (uint32_t)c.idx.size();
+        for (uint32_t j = 0; j < m.n; ++j) {
+            m.ptr[j] = mats[c.idx[j]];
+            m.width[j] = (uint32_t)widths[c.idx[j]];
+        }
+        LSP_HIP(launch_hash_rows(m, c.height, layers + 2 * (H - c.height), ctx->rc29_dev, ctx->p2.L, st));
+    }
+    size_t off = 0, len = H, next = 1;
+    while (len > 1) {
+        if (next == cls.size()) {  // no class left: the plain tree, its one-workgroup top included
+            LSP_HIP(launch_merkle_tree(layers + off, len, ctx->rc29_dev, ctx->p2.L, st));
+            break;
+        }
+        const size_t nout = len / 2;
+        Fr* dst = layers + off + len;
+        if (cls[next].height == nout) {
+            LSP_HIP(launch_merkle_inject(layers + off, dst, dst, nout, ctx->rc29_dev, ctx->p2.L, st));
+            ++next;
+        } else
+            LSP_HIP(launch_merkle_level(layers + off, dst, nout, ctx->rc29_dev, ctx->p2.L, st));
+        off += len;
+        len = nout;
+    }
+    return d2h_fr(ctx, layers + 2 * H - 2);
+}
+
+bool verify_mixed_host(const lsp_ctx* ctx, const Fr& root, const std::vector<HeightClass>& cls, const size_t* widths,
+                       size_t nmats, size_t index, const lsp_fr* rows, const lsp_fr* path) {
+    std::vector<size_t> at(nmats + 1, 0);  // matrix k's row starts at rows[at[k]] (the caller's order)
+    for (size_t k = 0; k < nmats; ++k) at[k + 1] = at[k] + widths[k];
+    auto class_hash = [&](const HeightClass& c) {
+        std::vector<Fr> v;
+        for (size_t k : c.idx)
+            for (size_t e = at[k]; e < at[k + 1]; ++e) v.push_back(to_fr(rows[e]));
+        return ctx->p2.hash(v.data(), v.size());
+    };
+    Fr cur = class_hash(cls[0]);
+    size_t next = 1, len = cls[0].height;
+    for (uint32_t k = 0; len > 1; ++k) {
+        const Fr sib = to_fr(path[k]);
+        cur = ((index >> k) & 1) ? ctx->p2.compress(sib, cur) : ctx->p2.compress(cur, sib);
+        len >>= 1;
+        if (next < cls.size() && cls[next].height == len) cur = ctx->p2.compress(cur, class_hash(cls[next++]));
+    }
+    return fr_eq(cur, root);
+}
+
+}  // namespace lsp

@@ -99,6 +99,27 @@ void resolve_timings(lsp_ctx* ctx);
 // and the host's tree top
 Fr commit_device(lsp_ctx* ctx, const MatList& m, size_t height, Fr* layers, const FoldSpec* fold = nullptr,
                  const std::function<void(hipEvent_t)>* side = nullptr);
+// Mixed-height batches (merkle_mixed.cpp; U14).  A class = the matrices of one
+// height, by the caller's indices in the caller's order; classes tallest first
+// (p3's stable sort by height).  height_classes checks the batch: LSP_E_SIZE
+// for a height that is no power of two or above 2^40 and for a matrix beyond
+// 2^48 elements, LSP_E_ARG for no matrix, a width outside [1, 2^20] (MatList
+// holds widths as 32 bits) or a ninth matrix in a class (MatList's limit).
+struct HeightClass {
+    size_t height;
+    std::vector<size_t> idx;
+};
+std::vector<HeightClass> height_classes(const size_t* widths, const size_t* heights, size_t nmats);
+// every class's row digests, then the levels from the leaves to the root with
+// each class injected at the level of its height, all on the context's stream;
+// mats: device matrices, by the caller's indices.  layers: 2 * cls[0].height - 1
+// digests, the layers after injection.  Returns the root.
+Fr commit_mixed_device(lsp_ctx* ctx, const std::vector<HeightClass>& cls, const Fr* const* mats, const size_t* widths,
+                       Fr* layers);
+// Mmcs::verify_batch of such a batch on the host: rows = one opened row per
+// matrix in the caller's order, path = log2(cls[0].height) digests
+bool verify_mixed_host(const lsp_ctx* ctx, const Fr& root, const std::vector<HeightClass>& cls, const size_t* widths,
+                       size_t nmats, size_t index, const lsp_fr* rows, const lsp_fr* path);
 // prep (optional): the committed preprocessed matrix -- a tree of ctx itself over
 // exactly one matrix of height h << log_blowup (lsp_preprocess's, or an
 // lsp_merkle_commit over a caller-made LDE); the proof then opens it too (LSPPRF03)

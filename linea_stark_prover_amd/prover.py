@@ -613,8 +613,12 @@ class Radix2DitParallel:
 
 
 class MerkleTree:
-    def __init__(self, ctx: Context, handle, height: int, widths: Sequence[int]):
+    def __init__(self, ctx: Context, handle, height: int, widths: Sequence[int],
+                 heights: Optional[Sequence[int]] = None):
+        """height: of the tallest matrices (the number of leaves); heights: per
+        matrix in the caller's order (None: all `height`)"""
         self.ctx, self.handle, self.height, self.widths = ctx, handle, height, list(widths)
+        self.heights = [height] * len(self.widths) if heights is None else list(heights)
 
     def __del__(self):
         if getattr(self, "handle", None):
@@ -634,18 +638,28 @@ class MerkleTreeMmcs:
         self.ctx = ctx
 
     def commit(self, mats: Sequence[np.ndarray]) -> Tuple[np.ndarray, MerkleTree]:
+        """Matrices of one height, or of several (each a power of two): the
+        tallest make the leaves, the shorter ones are injected at the level of
+        their height (lsp_merkle_commit_mixed)."""
         mats = [_fr_arr(m) for m in mats]
-        hgt = mats[0].shape[0]
-        assert all(m.shape[0] == hgt for m in mats), "equal heights only"
+        hs = [m.shape[0] for m in mats]
+        hgt = max(hs)
         ptrs = (ctypes.c_void_p * len(mats))(*[_ptr(m) for m in mats])
         widths = (ctypes.c_size_t * len(mats))(*[m.shape[1] for m in mats])
         root = np.zeros((1, 4), np.uint64)
         t = ctypes.c_void_p()
-        self.ctx._chk(L.lib().lsp_merkle_commit(self.ctx.h, ptrs, widths, len(mats), hgt, L.LSP_MEM_HOST,
-                                                _ptr(root), ctypes.byref(t)))
-        return root, MerkleTree(self.ctx, t, hgt, [m.shape[1] for m in mats])
+        if all(h == hgt for h in hs):
+            self.ctx._chk(L.lib().lsp_merkle_commit(self.ctx.h, ptrs, widths, len(mats), hgt, L.LSP_MEM_HOST,
+                                                    _ptr(root), ctypes.byref(t)))
+        else:
+            heights = (ctypes.c_size_t * len(mats))(*hs)
+            self.ctx._chk(L.lib().lsp_merkle_commit_mixed(self.ctx.h, ptrs, widths, heights, len(mats),
+                                                          L.LSP_MEM_HOST, _ptr(root), ctypes.byref(t)))
+        return root, MerkleTree(self.ctx, t, hgt, [m.shape[1] for m in mats], hs)
 
     def open_batch(self, index: int, tree: MerkleTree) -> Tuple[List[np.ndarray], np.ndarray]:
+        """one row per matrix in the caller's order (row index >> log2(height /
+        heights[j]) of matrix j) and the log2(height) sibling digests"""
         rows = np.zeros((sum(tree.widths), 4), np.uint64)
         path = np.zeros((max(tree.height.bit_length() - 1, 1), 4), np.uint64)
         self.ctx._chk(L.lib().lsp_merkle_open(tree.handle, index, _ptr(rows), _ptr(path)))
@@ -656,12 +670,25 @@ class MerkleTreeMmcs:
         return out, path[:tree.height.bit_length() - 1]
 
     def verify_batch(self, root: np.ndarray, widths: Sequence[int], log_height: int, index: int,
-                     rows: Sequence[np.ndarray], path: np.ndarray) -> bool:
+                     rows: Sequence[np.ndarray], path: np.ndarray, heights: Optional[Sequence[int]] = None) -> bool:
+        """heights (per matrix, the caller's order): a batch of several heights,
+        the tallest 2^log_height.  Bad dimensions raise; a rejection is False."""
         flat = _fr_arr(np.concatenate([_fr_arr(r).reshape(-1, 4) for r in rows]))
         ws = (ctypes.c_size_t * len(widths))(*widths)
         p = _fr_arr(path).reshape(-1, 4) if log_height else np.zeros((1, 4), np.uint64)
-        rc = L.lib().lsp_merkle_verify(self.ctx.h, _ptr(_fr_arr(root)), ws, len(widths), log_height, index,
-                                       _ptr(flat), _ptr(p))
+        if heights is None:
+            rc = L.lib().lsp_merkle_verify(self.ctx.h, _ptr(_fr_arr(root)), ws, len(widths), log_height, index,
+                                           _ptr(flat), _ptr(p))
+            return rc == L.LSP_OK
+        if len(heights) != len(widths) or not widths or max(heights) != 1 << log_height:
+            raise ValueError("heights do not fit the batch: one per matrix, the tallest 2^log_height")
+        if flat.shape[0] != sum(widths) or p.shape[0] < max(log_height, 1):
+            raise ValueError("rows or path of the wrong size for these dimensions")
+        hs = (ctypes.c_size_t * len(widths))(*heights)
+        rc = L.lib().lsp_merkle_verify_mixed(self.ctx.h, _ptr(_fr_arr(root)), ws, hs, len(widths), index,
+                                             _ptr(flat), _ptr(p))
+        if rc not in (L.LSP_OK, L.LSP_E_VERIFY):
+            L.check(rc)
         return rc == L.LSP_OK
 
 

@@ -34,7 +34,7 @@ impl Default for HipMmcs {
 pub struct HipTree<M> {
     tree: *mut sys::lsp_tree,
     leaves: Vec<M>,
-    height: usize,
+    height: usize, // of the tallest matrices
     widths: Vec<usize>,
 }
 
@@ -51,7 +51,12 @@ impl<M> Drop for HipTree<M> {
 #[derive(Debug)]
 pub enum HipMmcsError {
     WrongBatchSize,
-    UnequalHeights,
+    WrongWidth,
+    /// heights are powers of two, the library-wide rule (p3 pads others)
+    HeightNotPowerOfTwo,
+    IndexOutOfRange,
+    /// a batch of several heights beyond lsp_merkle_commit_mixed's limits
+    UnsupportedBatch,
     WrongProofLength,
     RootMismatch,
 }
@@ -62,36 +67,59 @@ impl Mmcs<Val> for HipMmcs {
     type Proof = Vec<[Val; 1]>;
     type Error = HipMmcsError;
 
-    /// lsp_merkle_commit: leaf i = hash_iter(row i of every matrix, in order),
-    /// nodes = compress(left, right).  Every caller in this prover commits
-    /// matrices of one height (trace; quotient chunks; one FRI round).
+    /// lsp_merkle_commit_mixed: the tallest matrices make the leaves (leaf i =
+    /// hash_iter(row i of each, in order)); the matrices of every smaller
+    /// height are hashed row by row and injected at the level with as many
+    /// nodes, node = compress(compress(left, right), hash_iter(rows)) -- p3's
+    /// MerkleTree::new.  Heights are powers of two (the library-wide rule).
+    /// Matrices of one height -- every commit of this prover: trace, quotient
+    /// chunks, one FRI round -- go to lsp_merkle_commit, which computes the
+    /// same tree byte for byte and finishes its top on the host.
     fn commit<M: Matrix<Val>>(&self, inputs: Vec<M>) -> (Self::Commitment, Self::ProverData<M>) {
         assert!(!inputs.is_empty(), "HipMmcs::commit of no matrices");
-        let height = inputs[0].height();
-        assert!(inputs.iter().all(|m| m.height() == height), "HipMmcs commits matrices of one height");
         // any M: Matrix -> one contiguous host copy per matrix for the upload
         // (host memory holds the matrices twice while this runs)
         let staged: Vec<Vec<Val>> = inputs.iter().map(|m| m.rows().flatten().collect()).collect();
         let ptrs: Vec<*const sys::lsp_fr> = staged.iter().map(|v| fr_ptr(v)).collect();
         let widths: Vec<usize> = inputs.iter().map(|m| m.width()).collect();
+        let heights: Vec<usize> = inputs.iter().map(|m| m.height()).collect();
+        let height = *heights.iter().max().unwrap();
         let mut root = [Val::ZERO];
         let mut tree: *mut sys::lsp_tree = std::ptr::null_mut();
-        let rc = unsafe {
-            sys::lsp_merkle_commit(
-                self.ctx.raw(),
-                ptrs.as_ptr(),
-                widths.as_ptr(),
-                ptrs.len(),
-                height,
-                sys::LSP_MEM_HOST,
-                fr_ptr_mut(&mut root),
-                &mut tree,
-            )
-        };
-        self.ctx.check(rc, "lsp_merkle_commit");
+        if heights.iter().all(|&h| h == height) {
+            let rc = unsafe {
+                sys::lsp_merkle_commit(
+                    self.ctx.raw(),
+                    ptrs.as_ptr(),
+                    widths.as_ptr(),
+                    ptrs.len(),
+                    height,
+                    sys::LSP_MEM_HOST,
+                    fr_ptr_mut(&mut root),
+                    &mut tree,
+                )
+            };
+            self.ctx.check(rc, "lsp_merkle_commit");
+        } else {
+            let rc = unsafe {
+                sys::lsp_merkle_commit_mixed(
+                    self.ctx.raw(),
+                    ptrs.as_ptr(),
+                    widths.as_ptr(),
+                    heights.as_ptr(),
+                    ptrs.len(),
+                    sys::LSP_MEM_HOST,
+                    fr_ptr_mut(&mut root),
+                    &mut tree,
+                )
+            };
+            self.ctx.check(rc, "lsp_merkle_commit_mixed");
+        }
         (Hash::from(root), HipTree { tree, leaves: inputs, height, widths })
     }
 
+    /// Row `index >> log2(height / h_j)` of every matrix, in commit order, and
+    /// the log2(height) siblings; `index` counts the tallest matrices' rows.
     fn open_batch<M: Matrix<Val>>(&self, index: usize, d: &HipTree<M>) -> (Vec<Vec<Val>>, Self::Proof) {
         let mut rows = vec![Val::ZERO; d.widths.iter().sum()];
         let mut path = vec![Val::ZERO; d.height.trailing_zeros() as usize];
@@ -110,7 +138,9 @@ impl Mmcs<Val> for HipMmcs {
         d.leaves.iter().collect()
     }
 
-    /// lsp_merkle_verify on the host (the verifier never needs a GPU)
+    /// lsp_merkle_verify (one height) or lsp_merkle_verify_mixed on the host
+    /// (the verifier never needs a GPU): `dimensions` in commit order, as
+    /// p3's MerkleTreeMmcs takes them
     fn verify_batch(
         &self,
         commit: &Self::Commitment,
@@ -122,25 +152,58 @@ impl Mmcs<Val> for HipMmcs {
         if dimensions.is_empty() || dimensions.len() != opened_values.len() {
             return Err(HipMmcsError::WrongBatchSize);
         }
-        let height = dimensions[0].height;
-        if !height.is_power_of_two() || dimensions.iter().any(|d| d.height != height) {
-            return Err(HipMmcsError::UnequalHeights);
+        if dimensions.iter().zip(opened_values).any(|(d, r)| d.width != r.len()) {
+            return Err(HipMmcsError::WrongWidth);
         }
+        if dimensions.iter().any(|d| !d.height.is_power_of_two()) {
+            return Err(HipMmcsError::HeightNotPowerOfTwo);
+        }
+        let height = dimensions.iter().map(|d| d.height).max().unwrap();
         let log_height = height.trailing_zeros();
         if proof.len() != log_height as usize {
             return Err(HipMmcsError::WrongProofLength);
         }
-        let widths: Vec<usize> = opened_values.iter().map(|r| r.len()).collect();
+        let widths: Vec<usize> = dimensions.iter().map(|d| d.width).collect();
         let rows: Vec<Val> = opened_values.iter().flatten().copied().collect();
         let path: Vec<Val> = proof.iter().map(|d| d[0]).collect();
         let root: [Val; 1] = (*commit).into();
+        // one height: lsp_merkle_verify, as before (any number of matrices)
+        if dimensions.iter().all(|d| d.height == height) {
+            let rc = unsafe {
+                sys::lsp_merkle_verify(
+                    self.ctx.raw(),
+                    fr1(&root[0]),
+                    widths.as_ptr(),
+                    widths.len(),
+                    log_height,
+                    index,
+                    fr_ptr(&rows),
+                    fr_ptr(&path),
+                )
+            };
+            return match rc {
+                sys::LSP_OK => Ok(()),
+                sys::LSP_E_VERIFY => Err(HipMmcsError::RootMismatch),
+                _ => {
+                    self.ctx.check(rc, "lsp_merkle_verify");
+                    unreachable!()
+                }
+            };
+        }
+        if index >= height {
+            return Err(HipMmcsError::IndexOutOfRange);
+        }
+        if widths.iter().any(|&w| w == 0) {
+            return Err(HipMmcsError::WrongWidth);
+        }
+        let heights: Vec<usize> = dimensions.iter().map(|d| d.height).collect();
         let rc = unsafe {
-            sys::lsp_merkle_verify(
+            sys::lsp_merkle_verify_mixed(
                 self.ctx.raw(),
                 fr1(&root[0]),
                 widths.as_ptr(),
+                heights.as_ptr(),
                 widths.len(),
-                log_height,
                 index,
                 fr_ptr(&rows),
                 fr_ptr(&path),
@@ -149,8 +212,11 @@ impl Mmcs<Val> for HipMmcs {
         match rc {
             sys::LSP_OK => Ok(()),
             sys::LSP_E_VERIFY => Err(HipMmcsError::RootMismatch),
+            // what lsp_merkle_commit_mixed cannot have committed: more than 8
+            // matrices of one height, a width or height beyond its limits
+            sys::LSP_E_ARG | sys::LSP_E_SIZE => Err(HipMmcsError::UnsupportedBatch),
             _ => {
-                self.ctx.check(rc, "lsp_merkle_verify");
+                self.ctx.check(rc, "lsp_merkle_verify_mixed");
                 unreachable!()
             }
         }
