@@ -22,23 +22,26 @@ std::string bounds_fault_report() {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return "";
     (void)hipDeviceSynchronize();  // the call's kernels are done (any stream)
-    static const char* const files[] = {"k_ntt.hip", "k_hash.hip", "k_field.hip", "k_quotient.hip", "k_open.hip",
-                                        "k_witness.hip", "k_check.hip", "k_merkle_inject.hip", "fr29.hpp", "k_common.hpp",
-                                        "poseidon2_f29.hpp", "fr.hpp", "k_air_prog.hpp"};
-    static unsigned (*const readers[])() = {bounds_fault_k_ntt, bounds_fault_k_hash, bounds_fault_k_field,
-                                            bounds_fault_k_quotient, bounds_fault_k_open, bounds_fault_k_witness,
-                                            bounds_fault_k_check, bounds_fault_k_merkle_inject};
-    static const char* const tus[] = {"k_ntt.hip", "k_hash.hip", "k_field.hip", "k_quotient.hip", "k_open.hip",
-                                      "k_witness.hip", "k_check.hip", "k_merkle_inject.hip"};
+    // a new kernel file adds one line here; a header with an LSP_BOUNDS, one name below
+    static const struct {
+        const char* tu;
+        unsigned (*reader)();
+    } tus[] = {{"k_ntt.hip", bounds_fault_k_ntt},         {"k_hash.hip", bounds_fault_k_hash},
+               {"k_field.hip", bounds_fault_k_field},     {"k_quotient.hip", bounds_fault_k_quotient},
+               {"k_open.hip", bounds_fault_k_open},       {"k_witness.hip", bounds_fault_k_witness},
+               {"k_check.hip", bounds_fault_k_check},     {"k_merkle_inject.hip", bounds_fault_k_merkle_inject}};
+    static const char* const headers[] = {"fr29.hpp", "k_common.hpp", "poseidon2_f29.hpp", "fr.hpp", "k_air_prog.hpp"};
     std::string out;
-    for (size_t t = 0; t < sizeof readers / sizeof readers[0]; ++t) {
-        const unsigned v = readers[t]();
+    for (const auto& t : tus) {
+        const unsigned v = t.reader();
         if (!v) continue;
         std::string file = "file#" + std::to_string(v >> 16);
-        for (const char* f : files)
+        for (const auto& u : tus)
+            if (dbg::file_code(u.tu) == (v >> 16)) file = u.tu;
+        for (const char* f : headers)
             if (dbg::file_code(f) == (v >> 16)) file = f;
         out += (out.empty() ? "" : "; ") + std::string("device bounds check failed at ") + file + ":" +
-               std::to_string(v & 0xffffu) + " (kernels of " + tus[t] + ")";
+               std::to_string(v & 0xffffu) + " (kernels of " + t.tu + ")";
     }
     return out;
 }
@@ -304,39 +307,6 @@ int lsp_ctx_create(int device, const lsp_params* p, lsp_ctx** out) {
 }
 
 int lsp_ctx_destroy(lsp_ctx* ctx) {
-    if (!ctx) return LSP_OK;
-    delete ctx->comm;
-    ctx->comm = nullptr;
-    if (ctx->device == LSP_HOST_ONLY) {
-        delete ctx;
-        return LSP_OK;
-    }
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->side_stream) (void)hipStreamSynchronize(ctx->side_stream);
-    for (auto& kv : ctx->pool)
-        if (kv.second.p) (void)hipFree(kv.second.p);
-    for (auto& kv : ctx->hpool)
-        if (kv.second.p) (void)hipHostFree(kv.second.p);
-    for (auto& kv : ctx->twiddles) (void)hipFree(kv.second);
-    for (auto& kv : ctx->stage_ev) (void)hipEventDestroy(kv.second);
-    for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
-    for (auto& t : ctx->pending_timings) {
-        (void)hipEventDestroy(std::get<1>(t));
-        (void)hipEventDestroy(std::get<2>(t));
-    }
-    if (ctx->ev_near) (void)hipEventDestroy(ctx->ev_near);
-    if (ctx->ev_top) (void)hipEventDestroy(ctx->ev_top);
-    if (ctx->ev_warm) (void)hipEventDestroy(ctx->ev_warm);
-    if (ctx->side_stream) {
-        (void)hipStreamSynchronize(ctx->side_stream);
-        (void)hipEventDestroy(ctx->ev_wide);
-        (void)hipEventDestroy(ctx->ev_side);
-        (void)hipStreamDestroy(ctx->side_stream);
-    }
-    if (ctx->rc_dev) (void)hipFree(ctx->rc_dev);
-    if (ctx->rc29_dev) (void)hipFree(ctx->rc29_dev);
-    (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return LSP_OK;
 }
@@ -471,31 +441,17 @@ int lsp_merkle_commit(lsp_ctx* ctx, const lsp_fr* const* mats, const size_t* wid
         std::lock_guard<std::mutex> g(ctx->mu);
         need_gpu(ctx);
         log2_exact(height);
-        auto t = std::make_unique<lsp_tree>();
-        t->ctx = ctx;
-        t->height = height;
+        for (size_t k = 0; k < nmats; ++k) LSP_REQUIRE(widths[k] >= 1 && mats[k], LSP_E_ARG, "bad matrix");
+        const std::vector<size_t> heights(nmats, height);
+        auto t = new_tree(ctx, height, nmats, heights.data(), widths, mats, mem);
         MatList m{};
         m.n = (uint32_t)nmats;
         for (size_t k = 0; k < nmats; ++k) {
-            LSP_REQUIRE(widths[k] >= 1 && mats[k], LSP_E_ARG, "bad matrix");
-            Fr* d = nullptr;
-            LSP_HIP(hipMalloc(&d, height * widths[k] * sizeof(Fr)));
-            t->mats.push_back(d);
-            t->widths.push_back(widths[k]);
-            LSP_HIP(hipMemcpyAsync(d, mats[k], height * widths[k] * sizeof(Fr),
-                                   mem == LSP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                                   ctx->stream));
-            m.ptr[k] = d;
+            m.ptr[k] = t->mats[k];
             m.width[k] = (uint32_t)widths[k];
         }
-        LSP_HIP(hipMalloc(&t->layers, (2 * height - 1) * sizeof(Fr)));
         *root = from_fr(commit_device(ctx, m, height, t->layers));
-        if (tree)
-            *tree = t.release();
-        else {
-            for (auto* d : t->mats) (void)hipFree(d);
-            (void)hipFree(t->layers);
-        }
+        if (tree) *tree = t.release();
     });
 }
 
@@ -509,43 +465,14 @@ int lsp_preprocess(lsp_ctx* ctx, const lsp_fr* cols, size_t h, size_t wp, int me
         const uint32_t log_h = log2_exact(h);
         LSP_REQUIRE(h >= 2 && log_h + ctx->log_blowup <= 40, LSP_E_SIZE, "preprocessed height outside [2, 2^40 / blowup]");
         const size_t N = h << ctx->log_blowup;
-        // the tree and its device memory, freed on every path out but the last
-        struct Owned {
-            lsp_tree* t = new lsp_tree();
-            ~Owned() {
-                if (!t) return;
-                for (auto* d : t->mats) (void)hipFree(d);
-                (void)hipFree(t->layers);
-                delete t;
-            }
-        } own;
-        lsp_tree* t = own.t;
-        t->ctx = ctx;
-        t->height = N;
         const Fr* din = dev_in(ctx, cols, h * wp, mem, "api_in");
-        Fr* lde = nullptr;
-        if (hipMalloc(&lde, N * wp * sizeof(Fr)) != hipSuccess) {
-            (void)hipGetLastError();
-            throw LspError(LSP_E_OOM, "hipMalloc of the preprocessed LDE failed");
-        }
-        t->mats.push_back(lde);
-        t->widths.push_back(wp);
-        if (hipMalloc(&t->layers, (2 * N - 1) * sizeof(Fr)) != hipSuccess) {
-            (void)hipGetLastError();
-            t->layers = nullptr;
-            throw LspError(LSP_E_OOM, "hipMalloc of the preprocessed tree failed");
-        }
+        auto t = new_tree(ctx, N, 1, &N, &wp, nullptr, mem);
         // the LDE goes straight into the tree's buffer: no copy
         const std::vector<Fr> sh(wp, host_generator());
-        lde_device(ctx, din, h, wp, ctx->log_blowup, sh.data(), lde);
-        MatList m{};
-        m.n = 1;
-        m.ptr[0] = lde;
-        m.width[0] = (uint32_t)wp;
-        *commit_out = from_fr(commit_device(ctx, m, N, t->layers));
+        lde_device(ctx, din, h, wp, ctx->log_blowup, sh.data(), t->mats[0]);
+        *commit_out = from_fr(commit_device(ctx, one_mat(t->mats[0], (uint32_t)wp), N, t->layers));
         ctx->sync();  // the host-made tree top goes up asynchronously
-        *out = t;
-        own.t = nullptr;
+        *out = t.release();
     });
 }
 
@@ -566,15 +493,10 @@ int lsp_merkle_open(const lsp_tree* t, size_t index, lsp_fr* rows_out, lsp_fr* p
                                   t->widths[k] * sizeof(Fr), hipMemcpyDeviceToHost));
                 o += t->widths[k];
             }
-        if (path_out) {
-            size_t off = 0, len = t->height;
-            for (uint32_t i = 0; len > 1; ++i) {
-                LSP_HIP(hipMemcpy(path_out + i, t->layers + off + ((index >> i) ^ 1), sizeof(Fr),
-                                  hipMemcpyDeviceToHost));
-                off += len;
-                len >>= 1;
-            }
-        }
+        const TreeLayout lay{t->height};
+        if (path_out)
+            for (uint32_t l = 0, n = lay.levels(); l < n; ++l)
+                LSP_HIP(hipMemcpy(path_out + l, t->layers + lay.sibling(l, index), sizeof(Fr), hipMemcpyDeviceToHost));
     });
 }
 
@@ -582,17 +504,14 @@ int lsp_merkle_layer(const lsp_tree* t, uint32_t level, lsp_fr* out) {
     if (!t || !out) return LSP_E_ARG;
     lsp_ctx* ctx = t->ctx;
     return guarded(ctx, [&] {
-        size_t off = 0, len = t->height;
-        for (uint32_t i = 0; i < level; ++i) {
-            LSP_REQUIRE(len > 1, LSP_E_ARG, "level out of range");
-            off += len;
-            len >>= 1;
-        }
+        const TreeLayout lay{t->height};
+        LSP_REQUIRE(level <= lay.levels(), LSP_E_ARG, "level out of range");
         std::lock_guard<std::mutex> g(ctx->mu);
         need_gpu(ctx);
         // on the context's (non-blocking) stream: the host-made top layers are
         // uploaded asynchronously on it by the commit
-        LSP_HIP(hipMemcpyAsync(out, t->layers + off, len * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+        LSP_HIP(hipMemcpyAsync(out, t->layers + lay.offset(level), lay.len(level) * sizeof(Fr), hipMemcpyDeviceToHost,
+                               ctx->stream));
         LSP_HIP(hipStreamSynchronize(ctx->stream));
     });
 }
@@ -600,16 +519,17 @@ int lsp_merkle_layer(const lsp_tree* t, uint32_t level, lsp_fr* out) {
 int lsp_merkle_verify(const lsp_ctx* ctx, const lsp_fr* root, const size_t* widths, size_t nmats,
                       uint32_t log_height, size_t index, const lsp_fr* rows, const lsp_fr* path) {
     if (!ctx || !root || !widths || !rows || (log_height && !path)) return LSP_E_ARG;
-    size_t tot = 0;
-    for (size_t k = 0; k < nmats; ++k) tot += widths[k];
-    std::vector<Fr> leaf(tot);
-    for (size_t i = 0; i < tot; ++i) leaf[i] = to_fr(rows[i]);
-    Fr cur = ctx->p2.hash(leaf.data(), tot);
-    for (uint32_t i = 0; i < log_height; ++i) {
-        const Fr sib = to_fr(path[i]);
-        cur = ((index >> i) & 1) ? ctx->p2.compress(sib, cur) : ctx->p2.compress(cur, sib);
-    }
-    return fr_eq(cur, to_fr(*root)) ? LSP_OK : LSP_E_VERIFY;
+    bool ok = false;
+    const int rc = guarded(nullptr, [&] {
+        size_t tot = 0;
+        for (size_t k = 0; k < nmats; ++k) tot += widths[k];
+        const std::vector<Fr> leaf = to_frs(rows, tot);
+        const Fr got = merkle_path_root(
+            ctx->p2, ctx->p2.hash(leaf.data(), tot), index, log_height, [&](uint32_t l) { return to_fr(path[l]); },
+            no_injection);
+        ok = fr_eq(got, to_fr(*root));
+    });
+    return rc != LSP_OK ? rc : ok ? LSP_OK : LSP_E_VERIFY;
 }
 
 int lsp_merkle_commit_mixed(lsp_ctx* ctx, const lsp_fr* const* mats, const size_t* widths, const size_t* heights,
@@ -622,36 +542,9 @@ int lsp_merkle_commit_mixed(lsp_ctx* ctx, const lsp_fr* const* mats, const size_
         for (size_t k = 0; k < nmats; ++k) LSP_REQUIRE(mats[k], LSP_E_ARG, "null matrix");
         std::lock_guard<std::mutex> g(ctx->mu);
         need_gpu(ctx);
-        // the tree and its device memory, freed on every path out unless handed over
-        struct Owned {
-            lsp_tree* t = new lsp_tree();
-            ~Owned() {
-                if (!t) return;
-                for (auto* d : t->mats) (void)hipFree(d);
-                (void)hipFree(t->layers);
-                delete t;
-            }
-        } own;
-        lsp_tree* t = own.t;
-        t->ctx = ctx;
-        t->height = cls[0].height;
-        t->widths.assign(widths, widths + nmats);
-        t->heights.assign(heights, heights + nmats);
-        for (size_t k = 0; k < nmats; ++k) {
-            const size_t bytes = heights[k] * widths[k] * sizeof(Fr);
-            Fr* d = nullptr;
-            LSP_HIP(hipMalloc(&d, bytes));
-            t->mats.push_back(d);
-            LSP_HIP(hipMemcpyAsync(d, mats[k], bytes,
-                                   mem == LSP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                                   ctx->stream));
-        }
-        LSP_HIP(hipMalloc(&t->layers, (2 * t->height - 1) * sizeof(Fr)));
+        auto t = new_tree(ctx, cls[0].height, nmats, heights, widths, mats, mem);
         *root = from_fr(commit_mixed_device(ctx, cls, t->mats.data(), widths, t->layers));
-        if (tree) {
-            *tree = t;
-            own.t = nullptr;
-        }
+        if (tree) *tree = t.release();
     });
 }
 
@@ -673,17 +566,13 @@ int lsp_tree_dims(const lsp_tree* t, size_t* heights, size_t* widths, size_t cap
     const size_t nm = t->widths.size();
     if (n) *n = nm;
     for (size_t k = 0; k < nm && k < cap; ++k) {
-        if (heights) heights[k] = t->heights.empty() ? t->height : t->heights[k];
+        if (heights) heights[k] = t->heights[k];
         if (widths) widths[k] = t->widths[k];
     }
     return LSP_OK;
 }
 
 int lsp_tree_free(lsp_tree* t) {
-    if (!t) return LSP_OK;
-    if (t->ctx->device != LSP_HOST_ONLY) (void)hipSetDevice(t->ctx->device);
-    for (auto* d : t->mats) (void)hipFree(d);
-    (void)hipFree(t->layers);
     delete t;
     return LSP_OK;
 }

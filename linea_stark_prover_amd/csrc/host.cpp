@@ -12,6 +12,8 @@
 #include <sched.h>
 #endif
 
+#include "comm.hpp"  // ~lsp_ctx deletes its communicator
+
 namespace lsp {
 
 Fr host_generator() { return fr_from_u64(22); }
@@ -422,6 +424,39 @@ Air::ConsInfo Air::constraint_info(uint32_t j) const {
 }  // namespace lsp
 
 // ------------------------------------------------------------------ context
+// Also a half-built context's (lsp_ctx_create): the stream is the first thing
+// made on the device, so without one there is nothing else to release.
+lsp_ctx::~lsp_ctx() {
+    delete comm;
+    if (device == LSP_HOST_ONLY || !stream) return;
+    (void)hipSetDevice(device);
+    (void)hipStreamSynchronize(stream);
+    if (side_stream) (void)hipStreamSynchronize(side_stream);
+    for (auto& kv : pool)
+        if (kv.second.p) (void)hipFree(kv.second.p);
+    for (auto& kv : hpool)
+        if (kv.second.p) (void)hipHostFree(kv.second.p);
+    for (auto& kv : twiddles) (void)hipFree(kv.second);
+    for (auto& kv : stage_ev) (void)hipEventDestroy(kv.second);
+    for (hipEvent_t e : event_pool) (void)hipEventDestroy(e);
+    for (auto& t : pending_timings) {
+        (void)hipEventDestroy(std::get<1>(t));
+        (void)hipEventDestroy(std::get<2>(t));
+    }
+    if (ev_near) (void)hipEventDestroy(ev_near);
+    if (ev_top) (void)hipEventDestroy(ev_top);
+    if (ev_warm) (void)hipEventDestroy(ev_warm);
+    if (side_stream) {
+        (void)hipStreamSynchronize(side_stream);
+        (void)hipEventDestroy(ev_wide);
+        (void)hipEventDestroy(ev_side);
+        (void)hipStreamDestroy(side_stream);
+    }
+    if (rc_dev) (void)hipFree(rc_dev);
+    if (rc29_dev) (void)hipFree(rc29_dev);
+    (void)hipStreamDestroy(stream);
+}
+
 void* lsp_ctx::buf(const std::string& name, size_t bytes) {
     Buf& b = pool[name];
     if (b.cap < bytes) {

@@ -379,20 +379,24 @@ struct lsp_raw_trace {
     std::vector<std::vector<lsp::Fr>> b_filter;
 };
 
+// A committed batch: owns its device memory (freed on its context's device)
 struct lsp_tree {
-    lsp_ctx* ctx = nullptr;
-    size_t height = 0;                 // of the tallest matrices = the number of leaves
+    lsp_ctx* ctx;
+    size_t height;                     // of the tallest matrices = the number of leaves
     std::vector<size_t> widths;
-    std::vector<size_t> heights;       // per matrix (lsp_merkle_commit_mixed); empty: every matrix is `height` rows
+    std::vector<size_t> heights;       // per matrix
     // the row of matrix k that the opening at leaf `index` holds
     size_t row_of(size_t k, size_t index) const {
         size_t r = index;
-        if (!heights.empty())
-            for (size_t h = heights[k]; h < height; h <<= 1) r >>= 1;
+        for (size_t h = heights[k]; h < height; h <<= 1) r >>= 1;
         return r;
     }
-    lsp::Fr* layers = nullptr;         // device, 2*height - 1
+    lsp::Fr* layers = nullptr;         // device, TreeLayout{height}.size() digests
     std::vector<lsp::Fr*> mats;        // device copies (owned) of the committed matrices
+    lsp_tree(lsp_ctx* c, size_t leaves) : ctx(c), height(leaves) {}
+    lsp_tree(const lsp_tree&) = delete;
+    lsp_tree& operator=(const lsp_tree&) = delete;
+    ~lsp_tree();  // merkle_mixed.cpp, with new_tree
 };
 
 namespace lsp {
@@ -517,4 +521,8 @@ struct lsp_ctx {
     const uint4* twiddle29(uint32_t logH, bool inverse);
     lsp::HostPool& host_pool();
     void sync();
+    lsp_ctx() = default;
+    lsp_ctx(const lsp_ctx&) = delete;
+    lsp_ctx& operator=(const lsp_ctx&) = delete;
+    ~lsp_ctx();  // releases everything above (a half-built context's too)
 };

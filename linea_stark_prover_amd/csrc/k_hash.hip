@@ -13,6 +13,7 @@
 
 #include "k_common.hpp"
 #include "kernels.hpp"
+#include "p2_launch.hpp"
 #include "poseidon2_f29.hpp"
 #include "poseidon2_row.hpp"
 
@@ -220,90 +221,12 @@ hipError_t launch_rc_to_f29(const Fr* rc, F29* rc29, uint32_t n, hipStream_t st)
     return hipGetLastError();
 }
 
-// D = the S-box degree, | P2_GEN for caller-set linear layers (gen_lin)
-#define LSP_DISPATCH_D(L, KERNEL, ...)                                  \
-    do {                                                                \
-        if ((L).gen_lin) {                                              \
-            if ((L).sbox_degree == 17)                                  \
-                hipLaunchKernelGGL(KERNEL<17u | P2_GEN>, __VA_ARGS__);  \
-            else                                                        \
-                hipLaunchKernelGGL(KERNEL<11u | P2_GEN>, __VA_ARGS__);  \
-        } else if ((L).sbox_degree == 17)                               \
-            hipLaunchKernelGGL(KERNEL<17>, __VA_ARGS__);                \
-        else                                                            \
-            hipLaunchKernelGGL(KERNEL<11>, __VA_ARGS__);                \
-    } while (0)
-
-// (degree, lanes) dispatch.  A batch of at most COOP_MAX permutations runs one
-// state per DPP quad: 4 * COOP_MAX lanes = one wave per SIMD of the 256 CUs,
-// where the quad form's shorter critical path (30 vs 46 S-boxes) wins; wider
-// batches are throughput-bound and keep one state per lane.
-#define LSP_DISPATCH_DL(DEG, LANES, KERNEL, ...)                          \
-    do {                                                                  \
-        if ((LANES) == 4)                                                 \
-            hipLaunchKernelGGL((KERNEL<DEG, 4>), __VA_ARGS__);            \
-        else if ((LANES) == 2)                                            \
-            hipLaunchKernelGGL((KERNEL<DEG, 2>), __VA_ARGS__);            \
-        else                                                              \
-            hipLaunchKernelGGL((KERNEL<DEG, 1>), __VA_ARGS__);            \
-    } while (0)
-#define LSP_DISPATCH_DC(L, LANES, KERNEL, ...)                            \
-    do {                                                                  \
-        if ((L).gen_lin) {                                                \
-            if ((L).sbox_degree == 17)                                    \
-                LSP_DISPATCH_DL(17u | P2_GEN, LANES, KERNEL, __VA_ARGS__);\
-            else                                                          \
-                LSP_DISPATCH_DL(11u | P2_GEN, LANES, KERNEL, __VA_ARGS__);\
-        } else if ((L).sbox_degree == 17)                                 \
-            LSP_DISPATCH_DL(17u, LANES, KERNEL, __VA_ARGS__);             \
-        else                                                              \
-            LSP_DISPATCH_DL(11u, LANES, KERNEL, __VA_ARGS__);             \
-    } while (0)
-
-static size_t coop_max() {
-    static const size_t v = [] {
-        const char* e = std::getenv("LSP_COOP_MAX");
-        return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)16384;
-    }();
-    return v;
-}
-static unsigned coop_bs() {  // 0: by width (state_grid)
-    static const unsigned v = [] {
-        const char* e = std::getenv("LSP_COOP_BS");
-        return e ? (unsigned)std::strtoul(e, nullptr, 10) : 0u;
-    }();
-    return v;
-}
-#define COOP_MAX coop_max()
-// up to this many states a pair per state (2 lanes): at 32K states one wave per
-// SIMD with 168 instead of 230 products on each lane's critical path
-static size_t pair_max() {
-    static const size_t v = [] {
-        const char* e = std::getenv("LSP_PAIR_MAX");
-        return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)32768;
-    }();
-    return v;
-}
-static inline int lanes_for(size_t n) { return n <= COOP_MAX ? 4 : (n <= pair_max() ? 2 : 1); }
-
-// grid for n states: quads in 64-lane blocks (256 from 16K states: one wave
-// per SIMD), pairs and single lanes in 256-lane blocks
-static inline void state_grid(size_t n, int lanes, unsigned& blocks, unsigned& bs) {
-    if (lanes == 4) {
-        // 4 lanes per state.  At 16K states (one wave per SIMD of the chip) 64-lane
-        // blocks land two waves on some SIMDs (~2x the level's latency); 256-lane
-        // blocks, one per CU, spread them one per SIMD.  Narrower levels: 64.
-        bs = coop_bs() ? coop_bs() : (4 * n >= 65536 ? 256u : 64u);
-        blocks = nblocks(4 * n, bs);
-    } else {
-        bs = 256;
-        blocks = nblocks((size_t)lanes * n, bs);
-    }
-}
-
 hipError_t launch_permute(Fr* states, size_t n, const F29* rc, P2Layout L, hipStream_t st) {
     if (!n) return hipSuccess;
-    LSP_DISPATCH_D(L, k_permute, dim3(nblocks(n, 256)), dim3(256), 0, st, states, n, rc, L.rounds_f, L.rounds_p);
+    p2_dispatch(L, [&](auto d) {
+        hipLaunchKernelGGL(k_permute<decltype(d)::value>, dim3(nblocks(n, 256)), dim3(256), 0, st, states, n, rc,
+                           L.rounds_f, L.rounds_p);
+    });
     return hipGetLastError();
 }
 
@@ -313,11 +236,15 @@ hipError_t launch_hash_rows(const MatList& m, size_t nrows, Fr* out, const F29* 
     unsigned blocks, bs;
     state_grid(nrows, lanes, blocks, bs);
     if (m.n == 1)
-        LSP_DISPATCH_DC(L, lanes, k_hash_rows1, dim3(blocks), dim3(bs), 0, st, m.ptr[0], m.width[0], nrows, out, rc,
-                        L.rounds_f, L.rounds_p);
+        p2_dispatch(L, lanes, [&](auto d, auto ln) {
+            hipLaunchKernelGGL((k_hash_rows1<decltype(d)::value, decltype(ln)::value>), dim3(blocks), dim3(bs), 0, st,
+                               m.ptr[0], m.width[0], nrows, out, rc, L.rounds_f, L.rounds_p);
+        });
     else
-        LSP_DISPATCH_DC(L, lanes, k_hash_rows_multi, dim3(blocks), dim3(bs), 0, st, m, nrows, out, rc, L.rounds_f,
-                        L.rounds_p);
+        p2_dispatch(L, lanes, [&](auto d, auto ln) {
+            hipLaunchKernelGGL((k_hash_rows_multi<decltype(d)::value, decltype(ln)::value>), dim3(blocks), dim3(bs), 0,
+                               st, m, nrows, out, rc, L.rounds_f, L.rounds_p);
+        });
     return hipGetLastError();
 }
 
@@ -326,32 +253,35 @@ hipError_t launch_fold_hash(const FoldSpec& f, size_t nleaves, Fr* out, const F2
     const int lanes = lanes_for(nleaves);
     unsigned blocks, bs;
     state_grid(nleaves, lanes, blocks, bs);
-    LSP_DISPATCH_DC(L, lanes, k_fold_hash, dim3(blocks), dim3(bs), 0, st, f, nleaves, out, rc, L.rounds_f, L.rounds_p);
+    p2_dispatch(L, lanes, [&](auto d, auto ln) {
+        hipLaunchKernelGGL((k_fold_hash<decltype(d)::value, decltype(ln)::value>), dim3(blocks), dim3(bs), 0, st, f,
+                           nleaves, out, rc, L.rounds_f, L.rounds_p);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_calib_perm(Fr* out, size_t nthreads, uint32_t iters, const F29* rc, P2Layout L, hipStream_t st) {
-    LSP_DISPATCH_D(L, k_calib_perm, dim3(nblocks(nthreads, 256)), dim3(256), 0, st, out, iters, rc, L.rounds_f,
-                   L.rounds_p);
+    p2_dispatch(L, [&](auto d) {
+        hipLaunchKernelGGL(k_calib_perm<decltype(d)::value>, dim3(nblocks(nthreads, 256)), dim3(256), 0, st, out, iters,
+                           rc, L.rounds_f, L.rounds_p);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_grind(const Fr pre[3], uint32_t wlane, uint64_t base, uint64_t count, uint32_t bits, bool mont,
                         const F29* rc, P2Layout L, unsigned long long* best, hipStream_t st) {
     const unsigned blocks = 256 * 16;
-    LSP_DISPATCH_D(L, k_grind, dim3(blocks), dim3(256), 0, st, pre[0], pre[1], pre[2], wlane, base, count, bits,
-                   (uint32_t)mont, rc,
-                   L.rounds_f, L.rounds_p, best);
+    p2_dispatch(L, [&](auto d) {
+        hipLaunchKernelGGL(k_grind<decltype(d)::value>, dim3(blocks), dim3(256), 0, st, pre[0], pre[1], pre[2], wlane,
+                           base, count, bits, (uint32_t)mont, rc, L.rounds_f, L.rounds_p, best);
+    });
     return hipGetLastError();
 }
 
 // levels of at most this many nodes run the row form (k_merkle_level_row);
 // LSP_ROW_MAX=0 keeps the quad form
 static size_t row_max() {
-    static const size_t v = [] {
-        const char* e = std::getenv("LSP_ROW_MAX");
-        return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)1024;
-    }();
+    static const size_t v = p2_env_size("LSP_ROW_MAX", 1024);
     return v;
 }
 
@@ -369,8 +299,10 @@ hipError_t launch_merkle_level(const Fr* src, Fr* dst, size_t nout, const F29* r
     const int lanes = lanes_for(nout);
     unsigned blocks, bs;
     state_grid(nout, lanes, blocks, bs);
-    LSP_DISPATCH_DC(L, lanes, k_merkle_level, dim3(blocks), dim3(bs), 0, st, src, dst, nout, rc, L.rounds_f,
-                    L.rounds_p);
+    p2_dispatch(L, lanes, [&](auto d, auto ln) {
+        hipLaunchKernelGGL((k_merkle_level<decltype(d)::value, decltype(ln)::value>), dim3(blocks), dim3(bs), 0, st,
+                           src, dst, nout, rc, L.rounds_f, L.rounds_p);
+    });
     return hipGetLastError();
 }
 
@@ -401,8 +333,10 @@ hipError_t launch_merkle_tree(Fr* layers, size_t nleaves, const F29* rc, P2Layou
         len /= 2;
     }
     if (len > 1) {
-        LSP_DISPATCH_D(L, k_merkle_top, dim3(1), dim3(256), 0, st, layers, off, (uint32_t)len, rc, L.rounds_f,
-                       L.rounds_p);
+        p2_dispatch(L, [&](auto d) {
+            hipLaunchKernelGGL(k_merkle_top<decltype(d)::value>, dim3(1), dim3(256), 0, st, layers, off, (uint32_t)len,
+                               rc, L.rounds_f, L.rounds_p);
+        });
         return hipGetLastError();
     }
     return hipSuccess;

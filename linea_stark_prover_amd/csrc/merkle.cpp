@@ -229,8 +229,8 @@ Fr commit_device(lsp_ctx* ctx, const MatList& m, size_t height, Fr* layers, cons
     Fr* host;  // host layers, starting at device offset `off` (pinned)
     if (leaves_on_host) {
         const size_t w = m.width[0];
-        host = (Fr*)ctx->hbuf(top_buf_name(ctx), (2 * height - 1 + height * w) * sizeof(Fr));
-        Fr* rows = host + 2 * height - 1;
+        host = (Fr*)ctx->hbuf(top_buf_name(ctx), (TreeLayout{height}.size() + height * w) * sizeof(Fr));
+        Fr* rows = host + TreeLayout{height}.size();
         LSP_HIP(hipMemcpyAsync(rows, m.ptr[0], height * w * sizeof(Fr), hipMemcpyDeviceToHost, st));
         if (side) {  // nothing left on the GPU for this tree
             LSP_HIP(hipEventRecord(ctx->ev_wide, st));
@@ -251,7 +251,7 @@ Fr commit_device(lsp_ctx* ctx, const MatList& m, size_t height, Fr* layers, cons
                 LSP_HIP(hipEventRecord(ctx->ev_wide, st));
                 (*side)(ctx->ev_wide);
             }
-            return d2h_fr(ctx, layers + 2 * height - 2);
+            return d2h_fr(ctx, layers + TreeLayout{height}.root());
         }
         if (!ctx->ev_near) {
             LSP_HIP(hipEventCreateWithFlags(&ctx->ev_near, hipEventDisableTiming));
@@ -290,7 +290,7 @@ Fr commit_device(lsp_ctx* ctx, const MatList& m, size_t height, Fr* layers, cons
             len = len1 / 2;
             // fine-grained (coherent) pinned memory: the kernel's stores bypass the
             // GPU caches, so they are in host memory when the kernel completes
-            host = (Fr*)ctx->hbuf(top_buf_name(ctx) + "c", (2 * len - 1) * sizeof(Fr), hipHostMallocCoherent);
+            host = (Fr*)ctx->hbuf(top_buf_name(ctx) + "c", TreeLayout{len}.size() * sizeof(Fr), hipHostMallocCoherent);
             LSP_HIP(launch_merkle_level(layers + off, host, len, ctx->rc29_dev, ctx->p2.L, st));
             off += len1;
             gpu_level_on_host = true;
@@ -298,7 +298,7 @@ Fr commit_device(lsp_ctx* ctx, const MatList& m, size_t height, Fr* layers, cons
             if (!zerocopy_top()) levels_to(top);
             off = off1;
             len = len1;
-            host = (Fr*)ctx->hbuf(top_buf_name(ctx), (2 * len - 1) * sizeof(Fr));
+            host = (Fr*)ctx->hbuf(top_buf_name(ctx), TreeLayout{len}.size() * sizeof(Fr));
             LSP_HIP(hipMemcpyAsync(host, layers + off, len * sizeof(Fr), hipMemcpyDeviceToHost, st));
         }
         LSP_HIP(hipEventRecord(ctx->ev_top, st));

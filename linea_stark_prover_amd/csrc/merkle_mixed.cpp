@@ -33,10 +33,46 @@ std::vector<HeightClass> height_classes(const size_t* widths, const size_t* heig
     return cls;
 }
 
+}  // namespace lsp
+
+lsp_tree::~lsp_tree() {
+    if (ctx->device != LSP_HOST_ONLY) (void)hipSetDevice(ctx->device);
+    for (auto* d : mats) (void)hipFree(d);
+    (void)hipFree(layers);
+}
+
+namespace lsp {
+
+static Fr* dev_alloc_fr(size_t n, const char* what) {
+    Fr* d = nullptr;
+    if (hipMalloc(&d, n * sizeof(Fr)) != hipSuccess) {
+        (void)hipGetLastError();
+        throw LspError(LSP_E_OOM, std::string("hipMalloc of ") + what + " failed");
+    }
+    return d;
+}
+
+std::unique_ptr<lsp_tree> new_tree(lsp_ctx* ctx, size_t leaves, size_t nmats, const size_t* heights,
+                                   const size_t* widths, const lsp_fr* const* src, int mem) {
+    auto t = std::make_unique<lsp_tree>(ctx, leaves);
+    t->widths.assign(widths, widths + nmats);
+    t->heights.assign(heights, heights + nmats);
+    for (size_t k = 0; k < nmats; ++k) {
+        const size_t n = heights[k] * widths[k];
+        t->mats.push_back(dev_alloc_fr(n, "a tree's matrix"));
+        if (src)
+            LSP_HIP(hipMemcpyAsync(t->mats[k], src[k], n * sizeof(Fr),
+                                   mem == LSP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                                   ctx->stream));
+    }
+    t->layers = dev_alloc_fr(TreeLayout{leaves}.size(), "a tree's layers");
+    return t;
+}
+
 Fr commit_mixed_device(lsp_ctx* ctx, const std::vector<HeightClass>& cls, const Fr* const* mats, const size_t* widths,
                        Fr* layers) {
     hipStream_t st = ctx->stream;
-    const size_t H = cls[0].height;
+    const TreeLayout lay{cls[0].height};
     // every class's row digests, into the layer they enter: the leaves for the
     // tallest class, for the others the layer the injecting level then
     // overwrites in place.  The levels' dependent chain holds no sponge.
@@ -47,9 +83,9 @@ Fr commit_mixed_device(lsp_ctx* ctx, const std::vector<HeightClass>& cls, const 
             m.ptr[j] = mats[c.idx[j]];
             m.width[j] = (uint32_t)widths[c.idx[j]];
         }
-        LSP_HIP(launch_hash_rows(m, c.height, layers + 2 * (H - c.height), ctx->rc29_dev, ctx->p2.L, st));
+        LSP_HIP(launch_hash_rows(m, c.height, layers + lay.offset_of_len(c.height), ctx->rc29_dev, ctx->p2.L, st));
     }
-    size_t off = 0, len = H, next = 1;
+    size_t off = 0, len = lay.leaves, next = 1;
     while (len > 1) {
         if (next == cls.size()) {  // no class left: the plain tree, its one-workgroup top included
             LSP_HIP(launch_merkle_tree(layers + off, len, ctx->rc29_dev, ctx->p2.L, st));
@@ -65,7 +101,7 @@ Fr commit_mixed_device(lsp_ctx* ctx, const std::vector<HeightClass>& cls, const 
         off += len;
         len = nout;
     }
-    return d2h_fr(ctx, layers + 2 * H - 2);
+    return d2h_fr(ctx, layers + lay.root());
 }
 
 bool verify_mixed_host(const lsp_ctx* ctx, const Fr& root, const std::vector<HeightClass>& cls, const size_t* widths,
@@ -78,15 +114,15 @@ bool verify_mixed_host(const lsp_ctx* ctx, const Fr& root, const std::vector<Hei
             for (size_t e = at[k]; e < at[k + 1]; ++e) v.push_back(to_fr(rows[e]));
         return ctx->p2.hash(v.data(), v.size());
     };
-    Fr cur = class_hash(cls[0]);
-    size_t next = 1, len = cls[0].height;
-    for (uint32_t k = 0; len > 1; ++k) {
-        const Fr sib = to_fr(path[k]);
-        cur = ((index >> k) & 1) ? ctx->p2.compress(sib, cur) : ctx->p2.compress(cur, sib);
-        len >>= 1;
-        if (next < cls.size() && cls[next].height == len) cur = ctx->p2.compress(cur, class_hash(cls[next++]));
-    }
-    return fr_eq(cur, root);
+    const TreeLayout lay{cls[0].height};
+    size_t next = 1;
+    const Fr got = merkle_path_root(
+        ctx->p2, class_hash(cls[0]), index, lay.levels(), [&](uint32_t l) { return to_fr(path[l]); },
+        [&](uint32_t level, const Fr& cur) {
+            if (next == cls.size() || cls[next].height != lay.len(level)) return cur;
+            return ctx->p2.compress(cur, class_hash(cls[next++]));
+        });
+    return fr_eq(got, root);
 }
 
 }  // namespace lsp

@@ -322,7 +322,7 @@ struct Prover {
         trace_lde();
         quotient_setup();
         early_constraints();
-        tlay = ctx->fbuf("t_tree", 2 * s.S - 1);
+        tlay = ctx->fbuf("t_tree", TreeLayout{s.S}.size());
         T.begin("merkle tree");
         proof->troot = shard_root(
             ctx, comm, commit_device(ctx, one_mat(lde, (uint32_t)s.w), s.S, tlay, nullptr, early ? &side_fn : nullptr),
@@ -493,7 +493,7 @@ struct Prover {
             lde_device(ctx, qv, h, q, s.lb, shifts.data(), qlde, s.k0, s.nk);
         }
         T.end("coset_lde_batch (quotient)");
-        qlay = ctx->fbuf("q_tree", 2 * s.S - 1);
+        qlay = ctx->fbuf("q_tree", TreeLayout{s.S}.size());
         proof->qroot = shard_root(ctx, comm, commit_device(ctx, one_mat(qlde, (uint32_t)q), s.S, qlay), qtop,
                                   "quotient subtree roots");
         T.end("commit to quotient poly chunks");
@@ -739,7 +739,7 @@ struct Prover {
         pending = true;
         rounds.push_back(std::move(R));
         vo += 2 * ml;
-        to += 2 * ml - 1;
+        to += TreeLayout{ml}.size();
         len = m;
     }
 
@@ -915,13 +915,9 @@ struct Prover {
             mine.push_back(qi);
             const size_t li = idx - s.row0;
             auto P = [&](const Fr* p) { ptrs.push_back((uint64_t)(uintptr_t)p); };
-            auto path = [&](const Fr* lay, size_t leaves, size_t leaf) {
-                size_t off = 0, ln = leaves;
-                for (uint32_t i = 0; (1ull << i) < leaves; ++i) {
-                    P(lay + off + ((leaf >> i) ^ 1));
-                    off += ln;
-                    ln >>= 1;
-                }
+            auto path = [&](const Fr* layers, size_t leaves, size_t leaf) {
+                const TreeLayout lay{leaves};
+                for (uint32_t l = 0, n = lay.levels(); l < n; ++l) P(layers + lay.sibling(l, leaf));
             };
             for (size_t c = 0; c < w; ++c) P(lde + li * w + c);
             path(tlay, S, li);
@@ -1056,7 +1052,7 @@ lsp_proof* prove_shard(lsp_ctx* ctx, Comm& comm, const Fr* d_trace, size_t h, si
         P.play = prep->layers;
         P.wp = wp;
         P.proof->wp = (uint32_t)wp;
-        P.proot = d2h_fr(ctx, prep->layers + 2 * geo.N - 2);  // the root: the last of the 2N - 1 digests
+        P.proot = d2h_fr(ctx, prep->layers + TreeLayout{geo.N}.root());
     }
 
     P.commit_trace();

@@ -57,6 +57,45 @@ void fri_fold(lsp_ctx* ctx, const FoldSpec& f, size_t m);
 // alpha^k, k < n, and a row of opened values reduced by them: sum_c apw[c] ys[c], c < w
 std::vector<Fr> alpha_powers(const Fr& alpha, size_t n);
 Fr reduce_opened(const Fr* apw, const Fr* ys, size_t w);
+// ---- Merkle trees
+// Where a tree's digests live in its one array, leaves first: level l (the
+// leaves are level 0) holds leaves >> l nodes from offset(l) on.
+struct TreeLayout {
+    size_t leaves;  // a power of two
+    uint32_t levels() const {  // above the leaves = the length of a path
+        uint32_t n = 0;
+        while (((size_t)1 << n) < leaves) ++n;
+        return n;
+    }
+    size_t len(uint32_t level) const { return leaves >> level; }
+    size_t offset(uint32_t level) const { return 2 * leaves - (2 * leaves >> level); }
+    size_t offset_of_len(size_t n) const { return 2 * (leaves - n); }  // of the level with n nodes
+    size_t root() const { return 2 * leaves - 2; }
+    size_t size() const { return 2 * leaves - 1; }
+    // the path element of `level` in the opening at leaf `index`
+    size_t sibling(uint32_t level, size_t index) const { return offset(level) + ((index >> level) ^ 1); }
+};
+// The root a path leads to from the digest `cur` of leaf `index`: per level l <
+// levels, cur = compress(cur, sibling(l)) in the order bit l of index says,
+// then cur = after_level(l + 1, cur) -- where a mixed-height tree injects
+// (merkle_mixed.cpp), the identity for a plain one.
+template <class Sibling, class AfterLevel>
+Fr merkle_path_root(const P2Host& p2, Fr cur, size_t index, uint32_t levels, Sibling&& sibling,
+                    AfterLevel&& after_level) {
+    for (uint32_t l = 0; l < levels; ++l) {
+        const Fr sib = sibling(l);
+        cur = after_level(l + 1, ((index >> l) & 1) ? p2.compress(sib, cur) : p2.compress(cur, sib));
+    }
+    return cur;
+}
+inline Fr no_injection(uint32_t, const Fr& cur) { return cur; }
+// A tree of ctx with `leaves` leaves over nmats device matrices heights[k] x
+// widths[k], each filled from src[k] -- the caller's host or device memory as
+// `mem` says, on the context's stream -- or, with src null, left for the
+// caller to write; and its layers, yet to be hashed.  LSP_E_OOM when the
+// device has no room.  (merkle_mixed.cpp)
+std::unique_ptr<lsp_tree> new_tree(lsp_ctx* ctx, size_t leaves, size_t nmats, const size_t* heights,
+                                   const size_t* widths, const lsp_fr* const* src, int mem);
 // ---- merkle.cpp
 // one per proof in flight, for the proof's whole duration (the tree tops share the host's cores)
 struct ActiveProof {

@@ -46,12 +46,8 @@ bool mk_verify(const P2Host& p2, const Fr& root, size_t index, const Fr* leaf, s
                uint32_t expect) {
     const uint32_t pl = r.u32();
     if (pl != expect) return false;
-    Fr cur = p2.hash(leaf, nleaf);
-    for (uint32_t i = 0; i < pl; ++i) {
-        const Fr sib = r.fr();
-        cur = ((index >> i) & 1) ? p2.compress(sib, cur) : p2.compress(cur, sib);
-    }
-    return !r.bad && fr_eq(cur, root);
+    const Fr got = merkle_path_root(p2, p2.hash(leaf, nleaf), index, pl, [&](uint32_t) { return r.fr(); }, no_injection);
+    return !r.bad && fr_eq(got, root);
 }
 }  // namespace
 

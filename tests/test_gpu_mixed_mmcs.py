@@ -2,7 +2,10 @@
 its trees' layers and openings, against the two references of
 tests/mixed_mmcs_ref.py -- (a) big integers over the oracle's sponge for the
 small shapes, (b) the host's Poseidon2 on arrays for the 2^17-leaf tree whose
-injecting levels cross every lane form.  Everything is bit-exact.
+injecting levels cross every lane form.  Also the lane knobs on a tree that
+injects (one child process per setting) and the handles' life cycle at the
+smallest shapes, for plain, mixed and lsp_preprocess trees.  Everything is
+bit-exact.
 """
 import ctypes
 import os
@@ -179,6 +182,151 @@ def test_adversarial_words(gpu_ctx, pp):
     arrs = [A.mat(r) for r in rows]
     mats = [[[A.value(x) for x in row] for row in m] for m in rows]
     check_against_integers(gpu_ctx, arrs, R.commit(mats, pp), *commit_mixed(gpu_ctx, arrs))
+
+
+# ------------------------------------------- the lane knobs on a tree that injects
+# The knobs are read once per process, so each setting runs in a child.  With
+# LSP_COOP_MAX=4 LSP_PAIR_MAX=16 a 64-leaf tree's levels of 32 nodes take one
+# lane, 16 and 8 a pair, 4 and below a quad: all three forms of the plain and of
+# the injecting kernel; LSP_ROW_MAX=0 keeps the plain levels off the row form.
+KNOB_SETTINGS = {
+    "default": {},
+    "all_forms": {"LSP_COOP_MAX": "4", "LSP_PAIR_MAX": "16", "LSP_ROW_MAX": "0"},
+    "one_lane": {"LSP_COOP_MAX": "0", "LSP_PAIR_MAX": "0", "LSP_ROW_MAX": "0"},
+    "quads_to_32k": {"LSP_COOP_MAX": "32768", "LSP_COOP_BS": "256", "LSP_ROW_MAX": "0"},
+    "rows_beside_injecting_quads": {"LSP_COOP_MAX": "4", "LSP_PAIR_MAX": "16"},
+}
+KNOB_LEAVES = (0, 37, 63)
+
+KNOB_CHILD = r'''
+import json, sys
+sys.path.insert(0, sys.argv[1])
+sys.path.insert(0, sys.argv[1] + "/tests")
+from linea_stark_prover_amd.field import from_mont
+from linea_stark_prover_amd.prover import Context, MerkleTreeMmcs, StarkConfig
+import test_gpu_mixed_mmcs as T
+out = {}
+with Context(StarkConfig()) as ctx:
+    mmcs = MerkleTreeMmcs(ctx)
+    ladder, plain = T.knob_mats()
+    for name, (root, tree) in (("ladder", T.commit_mixed(ctx, T.to_arrays(ladder))),
+                               ("plain", mmcs.commit(T.to_arrays(plain)))):
+        opens = [mmcs.open_batch(i, tree) for i in T.KNOB_LEAVES]
+        out[name] = {"root": from_mont(root), "layers": [from_mont(tree.layer(k)) for k in range(7)],
+                     "opens": [[[from_mont(r) for r in rows], from_mont(path)] for rows, path in opens]}
+        del tree
+print(json.dumps(out))
+'''
+
+
+def knob_mats():
+    """the ladder 64, 32, ..., 1 (every level injects) and a plain two-matrix tree of 64 rows"""
+    rnd = random.Random(55)
+    return R.ladder(6, rnd, widths=(1, 2, 3, 7)), R.random_mats([(64, 3), (64, 2)], rnd)
+
+
+@pytest.fixture(scope="module")
+def knob_reference(pp):
+    ladder, plain = knob_mats()
+    want, oracle = R.commit(ladder, pp), O.merkle_commit(plain, pp)
+
+    def opens(f, tree):
+        return [[[list(r) for r in rows], list(path)] for rows, path in (f(tree, i) for i in KNOB_LEAVES)]
+
+    return {"ladder": {"root": [want.root], "layers": want.layers, "opens": opens(R.open, want)},
+            "plain": {"root": [oracle.root], "layers": [list(l) for l in oracle.layers],
+                      "opens": opens(O.merkle_open, oracle)}}
+
+
+_abnormal = []  # the setting whose child crashed or hung: no further child is started
+
+
+@pytest.mark.parametrize("name", list(KNOB_SETTINGS))
+def test_lane_knobs_on_injecting_and_plain_trees(knob_reference, name):
+    import json
+    assert not _abnormal, f"the child of {_abnormal} ended abnormally; not starting another"
+    knobs = ("LSP_COOP_MAX", "LSP_PAIR_MAX", "LSP_COOP_BS", "LSP_ROW_MAX")
+    env = {k: v for k, v in os.environ.items() if k not in knobs}
+    env.update(KNOB_SETTINGS[name])
+    try:
+        r = subprocess.run([sys.executable, "-c", KNOB_CHILD, ROOT], env=env, capture_output=True, text=True,
+                           timeout=120, cwd=ROOT)
+    except subprocess.TimeoutExpired:
+        _abnormal.append(name)
+        raise
+    if r.returncode < 0 or r.returncode > 128:
+        _abnormal.append(name)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    got = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+    for tree in ("ladder", "plain"):
+        for part in ("root", "layers", "opens"):
+            assert got[tree][part] == knob_reference[tree][part], (name, tree, part)
+
+
+# ------------------------------------------------ handle life cycle, smallest shapes
+def _lifecycle_trees(ctx, kind, leaves, pp):
+    """-> (root, tree, root of the same commit without a tree or None, reference layers,
+    reference open(i) -> (rows, path), heights, widths)"""
+    from linea_stark_prover_amd.field import GENERATOR
+    from linea_stark_prover_amd.prover import MerkleTreeMmcs
+    lib, rnd = _lib.lib(), random.Random(f"{kind}{leaves}")
+    if kind == "preprocess":  # leaves = the rows committed to; the tree is over their LDE
+        cols = to_arrays(R.random_mats([(leaves, 3)], rnd))[0]
+        pre = ctx.preprocess(cols)
+        lde = ctx.coset_lde_batch(cols, ctx.config.log_blowup, to_mont([GENERATOR]))
+        mats = [[from_mont(row) for row in lde]]
+        want = O.merkle_commit(mats, pp)
+        return pre.commit, pre.tree, None, want.layers, lambda i: O.merkle_open(want, i), [len(lde)], [3]
+    shapes = {"plain": [(leaves, w) for w in (2, 1, 7)],
+              "mixed": {1: [(1, 2), (1, 3)], 2: [(2, 1), (1, 3)], 8: [(8, 2), (2, 3), (8, 1), (1, 7)]}[leaves]}[kind]
+    mats = R.random_mats(shapes, rnd)
+    arrs = to_arrays(mats)
+    hs, ws = [h for h, _ in shapes], [w for _, w in shapes]
+    ptrs = (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    lone = np.zeros((1, 4), np.uint64)
+    if kind == "plain":
+        root, tree = MerkleTreeMmcs(ctx).commit(arrs)
+        ctx._chk(lib.lsp_merkle_commit(ctx.h, ptrs, _sizes(ws), len(arrs), leaves, _lib.LSP_MEM_HOST,
+                                       lone.ctypes.data, None))
+        want = O.merkle_commit(mats, pp)
+        return root, tree, lone, want.layers, lambda i: O.merkle_open(want, i), hs, ws
+    root, tree = commit_mixed(ctx, arrs)
+    ctx._chk(lib.lsp_merkle_commit_mixed(ctx.h, ptrs, _sizes(ws), _sizes(hs), len(arrs), _lib.LSP_MEM_HOST,
+                                         lone.ctypes.data, None))
+    want = R.commit(mats, pp)
+    return root, tree, lone, want.layers, lambda i: R.open(want, i), hs, ws
+
+
+@pytest.mark.parametrize("kind", ["plain", "mixed", "preprocess"])
+def test_handle_life_cycle_at_the_smallest_shapes(product_lib, pp, kind):
+    """a context of its own, so that its trees' and its own release are part of the test"""
+    from linea_stark_prover_amd.prover import Context, StarkConfig
+    lib, ctx = product_lib, Context(StarkConfig())
+    for leaves in (2, 8) if kind == "preprocess" else (1, 2, 8):
+        root, tree, lone, layers, ref_open, hs, ws = _lifecycle_trees(ctx, kind, leaves, pp)
+        H, levels = len(layers[0]), len(layers) - 1
+        assert tree.height == H and from_mont(root) == layers[-1]
+        if lone is not None:
+            assert lone.tobytes() == root.tobytes()
+        n, got_h, got_w = ctypes.c_size_t(), _sizes([0] * len(ws)), _sizes([0] * len(ws))
+        assert lib.lsp_tree_dims(tree.handle, got_h, got_w, len(ws), ctypes.byref(n)) == _lib.LSP_OK
+        assert (n.value, list(got_h), list(got_w)) == (len(ws), hs, ws)
+        for i in range(H):
+            rows = np.zeros((sum(ws), 4), np.uint64)
+            path = np.full((levels + 1, 4), 0xA5A5A5A5A5A5A5A5, np.uint64)  # one digest more than the path
+            assert lib.lsp_merkle_open(tree.handle, i, rows.ctypes.data, path.ctypes.data) == _lib.LSP_OK
+            want_rows, want_path = ref_open(i)
+            assert from_mont(rows) == [x for r in want_rows for x in r], (leaves, i)
+            assert from_mont(path[:levels]) == list(want_path) and len(want_path) == levels, (leaves, i)
+            assert (path[levels:] == 0xA5A5A5A5A5A5A5A5).all()  # (all of it where one leaf has an empty path)
+        for k in range(levels + 1):
+            assert from_mont(tree.layer(k)) == list(layers[k]), (leaves, k)
+        past = np.zeros((1, 4), np.uint64)
+        assert lib.lsp_merkle_layer(tree.handle, levels + 1, past.ctypes.data) == _lib.LSP_E_ARG
+        assert lib.lsp_tree_free(tree.handle) == _lib.LSP_OK
+        tree.handle = None
+    assert lib.lsp_ctx_destroy(ctx.h) == _lib.LSP_OK
+    ctx.h = None
 
 
 DBG_CHILD = r'''

@@ -79,6 +79,42 @@ def test_reference_equals_oracle_on_equal_heights(pp, log_h, nmats):
         assert O.merkle_verify(want.root, i, rows, path, pp)
 
 
+@pytest.mark.parametrize("log_h", [0, 1, 3])
+@pytest.mark.parametrize("nmats", [1, 3])
+def test_both_verifiers_walk_the_oracles_openings(product_lib, host_ctx, pp, log_h, nmats):
+    """lsp_merkle_verify and lsp_merkle_verify_mixed share one path walk: on an
+    equal-height batch both accept every opening of the oracle's tree and both
+    reject one flipped word anywhere in it, and a wrong index"""
+    H, widths = 1 << log_h, [1, 2, 7][:nmats]
+    mats = R.random_mats([(H, w) for w in widths], random.Random(1000 * log_h + nmats))
+    tree = O.merkle_commit(mats, pp)
+
+    def both(root, index, rows, path):
+        r, flat = to_mont([root]), to_mont([x for row in rows for x in row])
+        p = to_mont(path) if path else np.zeros((1, 4), np.uint64)
+        plain = product_lib.lsp_merkle_verify(host_ctx.h, r.ctypes.data, _sizes(widths), nmats, log_h, index,
+                                              flat.ctypes.data, p.ctypes.data)
+        assert plain == _verify(product_lib, host_ctx, root, widths, [H] * nmats, index, rows, path)
+        return plain
+
+    for i in range(H):
+        rows, path = O.merkle_open(tree, i)
+        rows, path = [list(r) for r in rows], list(path)
+        assert len(path) == log_h
+        assert both(tree.root, i, rows, path) == _lib.LSP_OK, i
+        assert both(tree.root ^ 1, i, rows, path) == _lib.LSP_E_VERIFY, i
+        for k in range(nmats):  # one flipped word in one element of each matrix's row
+            bad = [list(r) for r in rows]
+            bad[k][(i + k) % widths[k]] ^= 1 << (64 * (i % 4))
+            assert both(tree.root, i, bad, path) == _lib.LSP_E_VERIFY, (i, k)
+        for k in range(log_h):  # each path digest in turn
+            bad = list(path)
+            bad[k] ^= 1 << (64 * (k % 4))
+            assert both(tree.root, i, rows, bad) == _lib.LSP_E_VERIFY, (i, k)
+        for wrong in ({i ^ 1, (i + 1) % H, H - 1 - i} - {i}) if log_h else ():  # one leaf has one index
+            assert both(tree.root, wrong, rows, path) == _lib.LSP_E_VERIFY, (i, wrong)
+
+
 def test_array_reference_equals_integer_reference(product_lib, host_ctx, pp):
     """H = 2^5, a class at every level, one of them of two matrices"""
     rnd = random.Random(5)
