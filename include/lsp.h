@@ -290,6 +290,76 @@ int lsp_merkle_verify_mixed(const lsp_ctx *ctx, const lsp_fr *root, const size_t
 int lsp_tree_dims(const lsp_tree *tree, size_t *heights, size_t *widths, size_t cap, size_t *n);
 int lsp_tree_free(lsp_tree *tree);
 
+/* ------------------------------------------------------------------- Pcs */
+/* Pcs = TwoAdicFriPcs<Val, Dft, ValMmcs, ChallengeMmcs> (bin/src/config.rs)
+ * [EXT p3-fri two_adic_pcs.rs] over batches of matrices of unequal heights;
+ * the conventions are U15 of DESIGN.md section 3, the fork's p3-fri.
+ *
+ * lsp_challenger: the Challenger the caller of a Pcs drives -- HashChallenger<
+ * Val, Hash, 1> (bin/src/config.rs:23) on the host, with U8 as the context it
+ * was created from has it.  observe = observe / observe_slice, sample =
+ * sample, sample_bits = sample_bits.  The handle copies what it needs: it may
+ * outlive the context.  Every call returns LSP_E_ARG for a NULL or freed
+ * handle, lsp_challenger_free included. */
+typedef struct lsp_challenger lsp_challenger;
+int lsp_challenger_create(const lsp_ctx *ctx, lsp_challenger **out);
+int lsp_challenger_observe(lsp_challenger *challenger, const lsp_fr *values, size_t n);
+int lsp_challenger_sample(lsp_challenger *challenger, lsp_fr *out);
+int lsp_challenger_sample_bits(lsp_challenger *challenger, uint32_t bits, uint64_t *out);
+int lsp_challenger_free(lsp_challenger *challenger);
+/* Pcs::commit: matrix j is heights[j] x widths[j], row-major, the evaluations
+ * of its columns on the domain shifts[j] * H_heights[j] (shifts NULL: every
+ * shift is one).  Each is extended by log_blowup with LDE shift GENERATOR /
+ * shifts[j] -- bit-reversed evaluations on GENERATOR * H_N, N = heights[j] <<
+ * log_blowup -- and the LDEs are committed as one mixed-height tree
+ * (lsp_merkle_commit_mixed's).  LDEs and tree stay on the device: *out is an
+ * ordinary lsp_tree, for lsp_tree_dims (which reports the LDE heights),
+ * lsp_merkle_open, lsp_merkle_layer and lsp_tree_free.
+ * LSP_E_ARG / LSP_E_SIZE as lsp_merkle_commit_mixed on the LDE heights;
+ * LSP_E_SIZE for an LDE height below 2 * 2^(log_blowup + log_final_poly_len),
+ * which no FRI round could take in; LSP_E_ARG for a zero shift. */
+int lsp_pcs_commit(lsp_ctx *ctx, const lsp_fr *const *mats, const size_t *heights, const size_t *widths,
+                   const lsp_fr *shifts, size_t n, int mem, lsp_fr *commit_out, lsp_tree **out);
+/* Pcs::open over ntrees committed batches (trees of this context, in the
+ * order their commitments went into the transcript).  npoints holds one count
+ * per matrix -- every matrix of trees[0] in its commit order, then trees[1]'s,
+ * ... -- and may be 0; points holds the points themselves in that order.  The
+ * caller has observed the commitments and sampled the points on `challenger`;
+ * the call observes and samples what p3's open does (U15) and leaves the
+ * challenger where p3's is after open.
+ * Refused before any launch -- LSP_E_ARG: no tree, no point at all, no point on
+ * a matrix of the tallest height over all batches, a point z on its matrix's
+ * own LDE coset (z^N = GENERATOR^N; p3 divides by zero there); LSP_E_SIZE: an
+ * LDE height below 2 * 2^(log_blowup + log_final_poly_len). */
+typedef struct lsp_pcs_proof lsp_pcs_proof;
+int lsp_pcs_open(lsp_ctx *ctx, const lsp_tree *const *trees, size_t ntrees, const size_t *npoints,
+                 const lsp_fr *points, lsp_challenger *challenger, lsp_pcs_proof **out);
+/* the opened values p(z), flat in [batch][matrix][point][column] order; the
+ * array lives as long as the proof */
+int lsp_pcs_proof_opened_values(const lsp_pcs_proof *proof, const lsp_fr **values, size_t *n);
+/* Wire format "LSPPCS01" (DESIGN.md section 9).  serialize: buf NULL asks for
+ * the length.  deserialize treats its input as untrusted and returns LSP_E_ARG
+ * for bytes that are no proof; what it accepts serializes back to the same
+ * bytes.  lsp_pcs_proof_free returns LSP_E_ARG for a NULL or freed handle. */
+int lsp_pcs_proof_serialize(const lsp_pcs_proof *proof, uint8_t *buf, size_t cap, size_t *len);
+int lsp_pcs_proof_deserialize(const uint8_t *buf, size_t len, lsp_pcs_proof **out);
+int lsp_pcs_proof_free(lsp_pcs_proof *proof);
+/* Pcs::verify on the host CPU; works on a host-only context.  commits: one
+ * root per batch; nmats: matrices per batch; heights / widths / npoints: one
+ * entry per matrix, batch after batch (heights as given to lsp_pcs_commit,
+ * not the LDE's); points as in lsp_pcs_open.  The challenger is where the
+ * prover's was when it called lsp_pcs_open.
+ * LSP_OK, or LSP_E_VERIFY with *failed_check (optional) naming the check:
+ *   1 header   5 body   12 query framing or trailing bytes   2 the counts
+ *   against the context and the tallest height   3 the shape against the
+ *   caller's batches   6 / 7 the proof-of-work witness   9 an input path's
+ *   length   8 an input opening   10 a commit-phase opening   11 the final
+ *   polynomial
+ * The refusals of lsp_pcs_open come back as LSP_E_ARG / LSP_E_SIZE here too. */
+int lsp_pcs_verify(const lsp_ctx *ctx, const lsp_fr *commits, size_t nbatches, const size_t *nmats,
+                   const size_t *heights, const size_t *widths, const size_t *npoints, const lsp_fr *points,
+                   const uint8_t *proof, size_t len, lsp_challenger *challenger, int *failed_check);
+
 /* ----------------------------------------------------------- FriFolder */
 /* TwoAdicFriGenericConfig::fold_matrix(beta, RowMajorMatrix(v, 2)) [EXT p3-fri]:
  * out[i] = (1/2 + beta/2 g^-bitrev(i)) v[2i] + (1/2 - beta/2 g^-bitrev(i)) v[2i+1],

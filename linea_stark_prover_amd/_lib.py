@@ -124,6 +124,28 @@ _SIGS = {
                                      ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
                                      ctypes.POINTER(ctypes.c_size_t)]),
     "lsp_tree_free": (ctypes.c_int, [ctypes.c_void_p]),
+    "lsp_challenger_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "lsp_challenger_observe": (ctypes.c_int, [ctypes.c_void_p, c_fr_p, ctypes.c_size_t]),
+    "lsp_challenger_sample": (ctypes.c_int, [ctypes.c_void_p, c_fr_p]),
+    "lsp_challenger_sample_bits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32,
+                                                  ctypes.POINTER(ctypes.c_uint64)]),
+    "lsp_challenger_free": (ctypes.c_int, [ctypes.c_void_p]),
+    "lsp_pcs_commit": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
+                                      ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t), c_fr_p,
+                                      ctypes.c_size_t, ctypes.c_int, c_fr_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "lsp_pcs_open": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t,
+                                    ctypes.POINTER(ctypes.c_size_t), c_fr_p, ctypes.c_void_p,
+                                    ctypes.POINTER(ctypes.c_void_p)]),
+    "lsp_pcs_proof_opened_values": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
+                                                   ctypes.POINTER(ctypes.c_size_t)]),
+    "lsp_pcs_proof_serialize": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                               ctypes.POINTER(ctypes.c_size_t)]),
+    "lsp_pcs_proof_deserialize": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]),
+    "lsp_pcs_proof_free": (ctypes.c_int, [ctypes.c_void_p]),
+    "lsp_pcs_verify": (ctypes.c_int, [ctypes.c_void_p, c_fr_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                                      ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
+                                      ctypes.POINTER(ctypes.c_size_t), c_fr_p, ctypes.c_char_p, ctypes.c_size_t,
+                                      ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     "lsp_fri_fold": (ctypes.c_int, [ctypes.c_void_p, c_fr_p, ctypes.c_size_t, c_fr_p, c_fr_p, ctypes.c_int]),
     "lsp_fri_fold_row": (None, [ctypes.c_size_t, ctypes.c_uint32, c_fr_p, c_fr_p, c_fr_p, c_fr_p]),
     "lsp_log_quotient_degree": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32,

@@ -29,7 +29,8 @@ std::string bounds_fault_report() {
     } tus[] = {{"k_ntt.hip", bounds_fault_k_ntt},         {"k_hash.hip", bounds_fault_k_hash},
                {"k_field.hip", bounds_fault_k_field},     {"k_quotient.hip", bounds_fault_k_quotient},
                {"k_open.hip", bounds_fault_k_open},       {"k_witness.hip", bounds_fault_k_witness},
-               {"k_check.hip", bounds_fault_k_check},     {"k_merkle_inject.hip", bounds_fault_k_merkle_inject}};
+               {"k_check.hip", bounds_fault_k_check},     {"k_merkle_inject.hip", bounds_fault_k_merkle_inject},
+               {"k_fri_mixed.hip", bounds_fault_k_fri_mixed}};
     static const char* const headers[] = {"fr29.hpp", "k_common.hpp", "poseidon2_f29.hpp", "fr.hpp", "k_air_prog.hpp"};
     std::string out;
     for (const auto& t : tus) {
@@ -575,6 +576,189 @@ int lsp_tree_dims(const lsp_tree* t, size_t* heights, size_t* widths, size_t cap
 int lsp_tree_free(lsp_tree* t) {
     delete t;
     return LSP_OK;
+}
+
+// ------------------------------------------------------------------ Pcs
+int lsp_challenger_create(const lsp_ctx* ctx, lsp_challenger** out) {
+    return guarded(nullptr, [&] {
+        LSP_REQUIRE(ctx && out, LSP_E_ARG, "bad challenger_create arguments");
+        *out = nullptr;
+        *out = new lsp_challenger(ctx);
+    });
+}
+
+extern "C++" {
+namespace {
+lsp_challenger* live(lsp_challenger* ch) {
+    LSP_REQUIRE(ch && ch->tag == lsp_challenger::TAG, LSP_E_ARG, "not a challenger handle");
+    return ch;
+}
+const lsp_pcs_proof* live(const lsp_pcs_proof* p) {
+    LSP_REQUIRE(p && p->tag == lsp_pcs_proof::TAG, LSP_E_ARG, "not a PCS proof handle");
+    return p;
+}
+// the flat arguments of lsp_pcs_open / lsp_pcs_verify as PcsRounds, checked (U15's refusals)
+PcsRounds pcs_rounds(const lsp_ctx* ctx, size_t nbatches, const std::function<size_t(size_t)>& nmats,
+                     const std::function<std::pair<size_t, size_t>(size_t, size_t)>& dims, const size_t* npoints,
+                     const lsp_fr* points) {
+    PcsRounds R;
+    LSP_REQUIRE(nbatches >= 1 && nbatches <= (1u << 16) && npoints, LSP_E_ARG, "a PCS opening needs 1 .. 2^16 batches");
+    R.batches.resize(nbatches);
+    size_t km = 0, kp = 0;
+    for (size_t b = 0; b < nbatches; ++b) {
+        const size_t nm = nmats(b);
+        LSP_REQUIRE(nm >= 1 && nm <= (1u << 16), LSP_E_ARG, "a batch needs 1 .. 2^16 matrices");
+        for (size_t k = 0; k < nm; ++k, ++km) {
+            PcsRounds::Mat m;
+            std::tie(m.N, m.width) = dims(b, k);
+            LSP_REQUIRE(npoints[km] <= (1u << 16), LSP_E_ARG, "more than 2^16 points on a matrix");
+            LSP_REQUIRE(npoints[km] == 0 || points, LSP_E_ARG, "null points");
+            for (size_t p = 0; p < npoints[km]; ++p) m.points.push_back(to_fr(points[kp++]));
+            R.batches[b].push_back(std::move(m));
+        }
+    }
+    R.check(ctx);
+    return R;
+}
+}  // namespace
+}
+
+int lsp_challenger_observe(lsp_challenger* ch, const lsp_fr* values, size_t n) {
+    return guarded(nullptr, [&] {
+        LSP_REQUIRE(values, LSP_E_ARG, "null values");
+        Challenger& c = live(ch)->ch;
+        for (size_t i = 0; i < n; ++i) c.observe(to_fr(values[i]));
+    });
+}
+
+int lsp_challenger_sample(lsp_challenger* ch, lsp_fr* out) {
+    return guarded(nullptr, [&] {
+        LSP_REQUIRE(out, LSP_E_ARG, "null output");
+        *out = from_fr(live(ch)->ch.sample());
+    });
+}
+
+int lsp_challenger_sample_bits(lsp_challenger* ch, uint32_t bits, uint64_t* out) {
+    return guarded(nullptr, [&] {
+        LSP_REQUIRE(out && bits <= 64, LSP_E_ARG, "bad sample_bits arguments");
+        *out = live(ch)->ch.sample_bits(bits);
+    });
+}
+
+int lsp_challenger_free(lsp_challenger* ch) {
+    return guarded(nullptr, [&] {
+        live(ch)->tag = 0;
+        delete ch;
+    });
+}
+
+int lsp_pcs_commit(lsp_ctx* ctx, const lsp_fr* const* mats, const size_t* heights, const size_t* widths,
+                   const lsp_fr* shifts, size_t n, int mem, lsp_fr* commit_out, lsp_tree** out) {
+    return guarded(ctx, [&] {
+        LSP_REQUIRE(ctx && mats && heights && widths && commit_out && out, LSP_E_ARG, "bad pcs_commit arguments");
+        LSP_REQUIRE(mem == LSP_MEM_HOST || mem == LSP_MEM_DEVICE, LSP_E_ARG,
+                    "mem must be LSP_MEM_HOST or LSP_MEM_DEVICE");
+        std::lock_guard<std::mutex> g(ctx->mu);
+        Fr root;
+        auto t = pcs_commit(ctx, mats, heights, widths, shifts, n, mem, &root);
+        *commit_out = from_fr(root);
+        *out = t.release();
+    });
+}
+
+int lsp_pcs_open(lsp_ctx* ctx, const lsp_tree* const* trees, size_t ntrees, const size_t* npoints, const lsp_fr* points,
+                 lsp_challenger* challenger, lsp_pcs_proof** out) {
+    return guarded(ctx, [&] {
+        LSP_REQUIRE(ctx && trees && npoints && out, LSP_E_ARG, "bad pcs_open arguments");
+        Challenger& ch = live(challenger)->ch;
+        *out = nullptr;
+        for (size_t b = 0; b < ntrees && b < (1u << 16); ++b)
+            LSP_REQUIRE(trees[b] && trees[b]->ctx == ctx, LSP_E_ARG, "a tree is null or belongs to another context");
+        std::lock_guard<std::mutex> g(ctx->mu);
+        PcsRounds R = pcs_rounds(
+            ctx, ntrees, [&](size_t b) { return trees[b]->mats.size(); },
+            [&](size_t b, size_t k) { return std::make_pair(trees[b]->heights[k], trees[b]->widths[k]); }, npoints,
+            points);
+        need_gpu(ctx);
+        *out = pcs_open(ctx, trees, R, ch).release();
+    });
+}
+
+int lsp_pcs_proof_opened_values(const lsp_pcs_proof* proof, const lsp_fr** values, size_t* n) {
+    return guarded(nullptr, [&] {
+        LSP_REQUIRE(values && n, LSP_E_ARG, "null output");
+        const lsp_pcs_proof* p = live(proof);
+        std::lock_guard<std::mutex> g(p->cache_mu);
+        if (p->ys_view.size() != p->ys.size())
+            for (const Fr& y : p->ys) p->ys_view.push_back(from_fr(y));
+        *values = p->ys_view.data();
+        *n = p->ys_view.size();
+    });
+}
+
+int lsp_pcs_proof_serialize(const lsp_pcs_proof* proof, uint8_t* buf, size_t cap, size_t* len) {
+    return guarded(nullptr, [&] {
+        LSP_REQUIRE(len, LSP_E_ARG, "null length");
+        const std::vector<uint8_t> b = pcs_serialize(*live(proof));
+        *len = b.size();
+        if (buf) {
+            LSP_REQUIRE(cap >= b.size(), LSP_E_ARG, "buffer too small");
+            std::memcpy(buf, b.data(), b.size());
+        }
+    });
+}
+
+int lsp_pcs_proof_deserialize(const uint8_t* buf, size_t len, lsp_pcs_proof** out) {
+    return guarded(nullptr, [&] {
+        LSP_REQUIRE(buf && out, LSP_E_ARG, "null");
+        *out = nullptr;
+        auto p = std::make_unique<lsp_pcs_proof>();
+        const int bad = pcs_parse(buf, len, *p);
+        LSP_REQUIRE(bad == 0, LSP_E_ARG, "not an LSPPCS01 proof (check " + std::to_string(bad) + ")");
+        *out = p.release();
+    });
+}
+
+int lsp_pcs_proof_free(lsp_pcs_proof* proof) {
+    return guarded(nullptr, [&] {
+        live(proof);
+        proof->tag = 0;
+        delete proof;
+    });
+}
+
+int lsp_pcs_verify(const lsp_ctx* ctx, const lsp_fr* commits, size_t nbatches, const size_t* nmats,
+                   const size_t* heights, const size_t* widths, const size_t* npoints, const lsp_fr* points,
+                   const uint8_t* proof, size_t len, lsp_challenger* challenger, int* failed_check) {
+    int rc = LSP_OK;
+    const int g = guarded(nullptr, [&] {
+        LSP_REQUIRE(ctx && commits && nmats && heights && widths && npoints && proof, LSP_E_ARG,
+                    "bad pcs_verify arguments");
+        Challenger& ch = live(challenger)->ch;
+        if (failed_check) *failed_check = 0;
+        const uint32_t lb = ctx->log_blowup;
+        std::vector<size_t> first(1, 0);  // batch b's matrices start at first[b] in the flat arrays
+        PcsRounds R = pcs_rounds(
+            ctx, nbatches,
+            [&](size_t b) {
+                first.push_back(first[b] + std::min<size_t>(nmats[b], 1u << 16));
+                return nmats[b];
+            },
+            [&](size_t b, size_t k) {
+                const size_t h = heights[first[b] + k];
+                LSP_REQUIRE(h <= (((size_t)1 << 40) >> lb), LSP_E_SIZE, "matrix height beyond 2^40 / blowup");
+                return std::make_pair(h << lb, widths[first[b] + k]);
+            },
+            npoints, points);
+        const std::vector<Fr> roots = to_frs(commits, nbatches);
+        const int v = pcs_verify_host(ctx, roots.data(), R, proof, len, ch);
+        if (v != 0) {
+            g_err = "PCS proof rejected at check " + std::to_string(v);
+            if (failed_check) *failed_check = v;
+            rc = LSP_E_VERIFY;
+        }
+    });
+    return g != LSP_OK ? g : rc;
 }
 
 int lsp_fri_fold(lsp_ctx* ctx, const lsp_fr* v, size_t len, const lsp_fr* beta, lsp_fr* out, int mem) {

@@ -399,6 +399,42 @@ struct lsp_tree {
     ~lsp_tree();  // merkle_mixed.cpp, with new_tree
 };
 
+// The two handles of the PCS (pcs.cpp; U15).  Both begin with a tag word that
+// every entry point checks, so that memory that is neither is refused rather
+// than read as one.
+// lsp_challenger: the host transcript a PCS caller drives (observe the
+// commitments, sample the points) and hands to lsp_pcs_open / lsp_pcs_verify.
+struct lsp_challenger {
+    static constexpr uint64_t TAG = 0x52474c484350534cull;  // "LSPCHLGR"
+    uint64_t tag = TAG;
+    lsp::P2Host p2;  // the creating context's hash, copied: the handle may outlive the context
+    lsp::Challenger ch;
+    explicit lsp_challenger(const lsp_ctx* ctx);  // pcs.cpp
+    lsp_challenger(const lsp_challenger&) = delete;
+    lsp_challenger& operator=(const lsp_challenger&) = delete;
+};
+// lsp_pcs_proof: TwoAdicFriPcs's (opened values, FriProof) over any number of
+// committed batches; wire format "LSPPCS01" 
+struct lsp_pcs_proof {
+    static constexpr uint64_t TAG = 0x464f525053435053ull;  // "SPCSPROF"
+    uint64_t tag = TAG;
+    struct Mat {
+        uint32_t width, npoints;
+    };
+    std::vector<std::vector<Mat>> shape;  // [batch][matrix]
+    std::vector<lsp::Fr> ys;              // [batch][matrix][point][column], flat
+    std::vector<lsp::Fr> roots, final_poly;
+    lsp::Fr pow_w;
+    struct Query {
+        std::vector<std::vector<lsp::Fr>> rows, paths;  // per batch: one row per matrix (caller's order), the path
+        std::vector<lsp::Fr> sib;                       // per round
+        std::vector<std::vector<lsp::Fr>> fpath;
+    };
+    std::vector<Query> queries;
+    mutable std::mutex cache_mu;
+    mutable std::vector<lsp_fr> ys_view;  // lsp_pcs_proof_opened_values' array, made on first use
+};
+
 namespace lsp {
 struct Comm;
 

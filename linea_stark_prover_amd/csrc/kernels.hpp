@@ -138,6 +138,17 @@ hipError_t launch_merkle_levels(Fr* layers, size_t nleaves, size_t stop_len, con
 hipError_t launch_merkle_inject(const Fr* src, const Fr* inj, Fr* dst, size_t nout, const F29* rc29, P2Layout L,
                                 hipStream_t st);
 
+// ------------------------------------------------------ k_fri_mixed.hip
+// FRI over inputs of unequal heights (U15): launch_fold_hash with the roll-in
+// fused.  v'[i] = fold(v)[i] + add[i] for i < 2 nleaves (add: the
+// reduced-opening vector as long as v', or nullptr) goes to f.vout and leaf
+// j = hash_iter(v'[2j], v'[2j+1]) to out, in the lane form a plain leaf batch
+// of nleaves takes
+hipError_t launch_fold_add_hash(const FoldSpec& f, const Fr* add, size_t nleaves, Fr* out, const F29* rc29, P2Layout L,
+                                hipStream_t st);
+// f.vout[i] = fold(v)[i] + add[i] for i < m (add nullable): the last fold, which no leaf kernel follows
+hipError_t launch_fri_fold_add(const FoldSpec& f, const Fr* add, size_t m, hipStream_t st);
+
 // --------------------------------------------------------- k_field.hip
 // out[i] = 1/in[i] (0 -> 0: a zero input leaves the other outputs as they
 // are); out != in.  Montgomery's trick over workgroup product trees, one
@@ -358,6 +369,7 @@ unsigned bounds_fault_k_open();
 unsigned bounds_fault_k_witness();
 unsigned bounds_fault_k_check();
 unsigned bounds_fault_k_merkle_inject();
+unsigned bounds_fault_k_fri_mixed();
 #endif
 // one matrix opened at npts points (the generic reduce of TwoAdicFriPcs::open):
 // ro[i] += sum_p (offys[p] - off[p] * sum_c apw[c] M[i][c]) * inv[p*n + i]

@@ -159,6 +159,32 @@ Fr commit_mixed_device(lsp_ctx* ctx, const std::vector<HeightClass>& cls, const 
 // matrix in the caller's order, path = log2(cls[0].height) digests
 bool verify_mixed_host(const lsp_ctx* ctx, const Fr& root, const std::vector<HeightClass>& cls, const size_t* widths,
                        size_t nmats, size_t index, const lsp_fr* rows, const lsp_fr* path);
+// GrindingChallenger::grind(bits) on the device, re-checked on (and applied to) the host transcript (prove.cpp)
+uint64_t grind_device(lsp_ctx* ctx, Challenger& ch, uint32_t bits);
+// ---- pcs.cpp: TwoAdicFriPcs over batches of unequal heights
+// One opening problem as commit, open and verify all see it: per batch the LDE
+// heights and widths of its matrices in the caller's order, per matrix its points.
+struct PcsRounds {
+    struct Mat {
+        size_t N, width;  // N: the LDE height
+        std::vector<Fr> points;
+    };
+    std::vector<std::vector<Mat>> batches;
+    size_t log_nmax = 0;  // of the tallest LDE over all batches (check sets it)
+    // the refusals of U15, before any launch: LSP_E_ARG / LSP_E_SIZE
+    void check(const lsp_ctx* ctx);
+};
+// the tree of the LDEs of n matrices heights[k] x widths[k] with domain shifts
+// shifts[k] (nullptr: all one), read from the caller's host or device memory
+std::unique_ptr<lsp_tree> pcs_commit(lsp_ctx* ctx, const lsp_fr* const* mats, const size_t* heights,
+                                     const size_t* widths, const lsp_fr* shifts, size_t n, int mem, Fr* root);
+// TwoAdicFriPcs::open of R.batches[b] = the matrices of trees[b]
+std::unique_ptr<lsp_pcs_proof> pcs_open(lsp_ctx* ctx, const lsp_tree* const* trees, PcsRounds& R, Challenger& ch);
+// 0 = accept, otherwise the failing check (host only).  commits: one root per batch
+int pcs_verify_host(const lsp_ctx* ctx, const Fr* commits, PcsRounds& R, const uint8_t* b, size_t n, Challenger& ch);
+std::vector<uint8_t> pcs_serialize(const lsp_pcs_proof& p);
+// 0, or the check that refused the bytes (1: header, 5: body, 12: queries or trailing bytes)
+int pcs_parse(const uint8_t* b, size_t n, lsp_pcs_proof& p);
 // prep (optional): the committed preprocessed matrix -- a tree of ctx itself over
 // exactly one matrix of height h << log_blowup (lsp_preprocess's, or an
 // lsp_merkle_commit over a caller-made LDE); the proof then opens it too (LSPPRF03)

@@ -10,6 +10,8 @@ Reference item                                   -> here
   p3_interpolation::interpolate_coset             -> Context.interpolate_coset
   TwoAdicFriPcs::open compute_inverse_denominators -> Context.inverse_denominators
   TwoAdicFriPcs::open reduce rows                 -> Context.open_reduce
+  Pcs = TwoAdicFriPcs commit/open/verify          -> TwoAdicFriPcs (batches of unequal heights, U15)
+  HashChallenger<Val, Hash, 1>                    -> HashChallenger
   p3_uni_stark::prove / verify (main.rs:80-96)    -> prove / verify
 
 Arrays are numpy uint64 with a trailing axis of 4 limbs (Montgomery form).
@@ -711,6 +713,127 @@ class TwoAdicFriGenericConfig:
         L.lib().lsp_fri_fold_row(index, log_height, _ptr(_fr_arr(beta)), _ptr(_fr_arr(e0)), _ptr(_fr_arr(e1)),
                                  _ptr(out))
         return out
+
+
+class HashChallenger:
+    """HashChallenger<Val, Hash, 1> (bin/src/config.rs:23) on the host, with U8
+    as `ctx` has it: the transcript a TwoAdicFriPcs caller drives."""
+
+    def __init__(self, ctx: Context):
+        self.handle = ctypes.c_void_p()
+        L.check(L.lib().lsp_challenger_create(ctx.h, ctypes.byref(self.handle)))
+
+    def __del__(self):
+        if getattr(self, "handle", None):
+            L.lib().lsp_challenger_free(self.handle)
+            self.handle = None
+
+    def observe(self, values):
+        """one element (4 limbs) or an array of them"""
+        v = _fr_arr(values).reshape(-1, 4)
+        if v.shape[0]:
+            L.check(L.lib().lsp_challenger_observe(self.handle, _ptr(v), v.shape[0]))
+
+    def sample(self) -> np.ndarray:
+        out = np.zeros((1, 4), np.uint64)
+        L.check(L.lib().lsp_challenger_sample(self.handle, _ptr(out)))
+        return out
+
+    def sample_bits(self, bits: int) -> int:
+        out = ctypes.c_uint64()
+        L.check(L.lib().lsp_challenger_sample_bits(self.handle, bits, ctypes.byref(out)))
+        return out.value
+
+
+def _flat_points(per_matrix):
+    """per matrix an array of points (k, 4) or None -> (counts, flat (n, 4) array)"""
+    pts = [np.zeros((0, 4), np.uint64) if p is None else _fr_arr(p).reshape(-1, 4) for p in per_matrix]
+    counts = (ctypes.c_size_t * max(len(pts), 1))(*[p.shape[0] for p in pts])
+    flat = np.ascontiguousarray(np.concatenate(pts + [np.zeros((1, 4), np.uint64)]))
+    return counts, flat
+
+
+class TwoAdicFriPcs:
+    """Pcs = TwoAdicFriPcs<Val, Dft, ValMmcs, ChallengeMmcs> (bin/src/config.rs)
+    over batches of matrices of unequal heights."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.last_check = 0  # the check that refused the last verify()'s proof (include/lsp.h), 0: none
+
+    def commit(self, mats, shifts=None, dims=None) -> Tuple[np.ndarray, MerkleTree]:
+        """mats: h_j x w_j x 4 arrays of evaluations on shifts[j] * H_(h_j) (shifts
+        None: all one) -- or, with dims = [(h_j, w_j)], device addresses of such
+        matrices.  Returns the commitment and the tree of the LDEs, whose
+        heights are the LDE's."""
+        if dims is None:
+            mats = [_fr_arr(m) for m in mats]
+            dims = [m.shape[:2] for m in mats]
+            ptrs, mem = [_ptr(m) for m in mats], L.LSP_MEM_HOST
+        else:
+            ptrs, mem = [int(p) for p in mats], L.LSP_MEM_DEVICE
+        n = len(ptrs)
+        cp = (ctypes.c_void_p * max(n, 1))(*ptrs)
+        hs = (ctypes.c_size_t * max(n, 1))(*[d[0] for d in dims])
+        ws = (ctypes.c_size_t * max(n, 1))(*[d[1] for d in dims])
+        sh = None if shifts is None else _fr_arr(shifts).reshape(-1, 4)
+        assert sh is None or sh.shape[0] == n, "one domain shift per matrix"
+        root = np.zeros((1, 4), np.uint64)
+        t = ctypes.c_void_p()
+        self.ctx._chk(L.lib().lsp_pcs_commit(self.ctx.h, cp, hs, ws, None if sh is None else _ptr(sh), n, mem,
+                                             _ptr(root), ctypes.byref(t)))
+        lde = [d[0] << self.ctx.config.log_blowup for d in dims]
+        return root, MerkleTree(self.ctx, t, max(lde), [d[1] for d in dims], lde)
+
+    def open(self, rounds, challenger: HashChallenger):
+        """rounds: [(tree, [points of matrix 0, of matrix 1, ...])], a matrix's
+        points a (k, 4) array or None.  Returns (opened values
+        [batch][matrix] -> (points, width, 4) array, the proof's LSPPCS01 bytes)."""
+        trees = (ctypes.c_void_p * max(len(rounds), 1))(*[t.handle for t, _ in rounds])
+        counts, flat = _flat_points([p for _, pts in rounds for p in pts])
+        for t, pts in rounds:
+            assert len(pts) == len(t.widths), "one list of points per committed matrix"
+        proof = ctypes.c_void_p()
+        self.ctx._chk(L.lib().lsp_pcs_open(self.ctx.h, trees, len(rounds), counts, _ptr(flat), challenger.handle,
+                                           ctypes.byref(proof)))
+        try:
+            vals, n = ctypes.c_void_p(), ctypes.c_size_t()
+            L.check(L.lib().lsp_pcs_proof_opened_values(proof, ctypes.byref(vals), ctypes.byref(n)))
+            ys = np.ctypeslib.as_array(ctypes.cast(vals, ctypes.POINTER(ctypes.c_uint64)),
+                                       (n.value, 4)).copy() if n.value else np.zeros((0, 4), np.uint64)
+            ln = ctypes.c_size_t()
+            L.check(L.lib().lsp_pcs_proof_serialize(proof, None, 0, ctypes.byref(ln)))
+            buf = ctypes.create_string_buffer(ln.value)
+            L.check(L.lib().lsp_pcs_proof_serialize(proof, buf, ln.value, ctypes.byref(ln)))
+        finally:
+            L.lib().lsp_pcs_proof_free(proof)
+        opened, o, k = [], 0, 0
+        for t, _ in rounds:
+            opened.append([])
+            for w in t.widths:
+                npts = counts[k]
+                opened[-1].append(ys[o:o + npts * w].reshape(npts, w, 4))
+                o += npts * w
+                k += 1
+        return opened, buf.raw[:ln.value]
+
+    def verify(self, rounds, proof: bytes, challenger: HashChallenger) -> bool:
+        """rounds: [(commitment, [(height, width, points)])] with the heights
+        given to commit.  A rejection is False (last_check names the check);
+        dimensions or points that open() refuses raise."""
+        mats = [m for _, ms in rounds for m in ms]
+        commits = _fr_arr(np.concatenate([_fr_arr(c).reshape(1, 4) for c, _ in rounds] or [np.zeros((1, 4), np.uint64)]))
+        nm = (ctypes.c_size_t * max(len(rounds), 1))(*[len(ms) for _, ms in rounds])
+        hs = (ctypes.c_size_t * max(len(mats), 1))(*[m[0] for m in mats])
+        ws = (ctypes.c_size_t * max(len(mats), 1))(*[m[1] for m in mats])
+        counts, flat = _flat_points([m[2] for m in mats])
+        check = ctypes.c_int(0)
+        rc = L.lib().lsp_pcs_verify(self.ctx.h, _ptr(commits), len(rounds), nm, hs, ws, counts, _ptr(flat), proof,
+                                    len(proof), challenger.handle, ctypes.byref(check))
+        self.last_check = check.value
+        if rc not in (L.LSP_OK, L.LSP_E_VERIFY):
+            L.check(rc)
+        return rc == L.LSP_OK
 
 
 def gen_permutation_trace(log_n: int, ncols: int, alpha: np.ndarray, delta: np.ndarray,
