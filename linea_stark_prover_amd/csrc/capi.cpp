@@ -30,7 +30,7 @@ std::string bounds_fault_report() {
                {"k_field.hip", bounds_fault_k_field},     {"k_quotient.hip", bounds_fault_k_quotient},
                {"k_open.hip", bounds_fault_k_open},       {"k_witness.hip", bounds_fault_k_witness},
                {"k_check.hip", bounds_fault_k_check},     {"k_merkle_inject.hip", bounds_fault_k_merkle_inject},
-               {"k_fri_mixed.hip", bounds_fault_k_fri_mixed}};
+               {"k_fri.hip", bounds_fault_k_fri}};
     static const char* const headers[] = {"fr29.hpp", "k_common.hpp", "poseidon2_f29.hpp", "fr.hpp", "k_air_prog.hpp"};
     std::string out;
     for (const auto& t : tus) {
@@ -451,7 +451,7 @@ int lsp_merkle_commit(lsp_ctx* ctx, const lsp_fr* const* mats, const size_t* wid
             m.ptr[k] = t->mats[k];
             m.width[k] = (uint32_t)widths[k];
         }
-        *root = from_fr(commit_device(ctx, m, height, t->layers));
+        *root = from_fr(commit_device(ctx, m, height, t->layers, host_tree_top(ctx)));
         if (tree) *tree = t.release();
     });
 }
@@ -471,7 +471,7 @@ int lsp_preprocess(lsp_ctx* ctx, const lsp_fr* cols, size_t h, size_t wp, int me
         // the LDE goes straight into the tree's buffer: no copy
         const std::vector<Fr> sh(wp, host_generator());
         lde_device(ctx, din, h, wp, ctx->log_blowup, sh.data(), t->mats[0]);
-        *commit_out = from_fr(commit_device(ctx, one_mat(t->mats[0], (uint32_t)wp), N, t->layers));
+        *commit_out = from_fr(commit_device(ctx, one_mat(t->mats[0], (uint32_t)wp), N, t->layers, host_tree_top(ctx)));
         ctx->sync();  // the host-made tree top goes up asynchronously
         *out = t.release();
     });
@@ -781,10 +781,7 @@ int lsp_fri_fold(lsp_ctx* ctx, const lsp_fr* v, size_t len, const lsp_fr* beta, 
 void lsp_fri_fold_row(size_t index, uint32_t log_height, const lsp_fr* beta, const lsp_fr* e0, const lsp_fr* e1,
                       lsp_fr* out) {
     if (!beta || !e0 || !e1 || !out) return;
-    const Fr s0 = fr_pow_u64(host_two_adic_generator(log_height + 1), host_bitrev(index, log_height));
-    const Fr a = to_fr(*e0), b = to_fr(*e1);
-    const Fr r = fr_add(a, fr_mul(fr_mul(fr_sub(to_fr(*beta), s0), fr_sub(b, a)), fr_inv(fr_sub(fr_neg(s0), s0))));
-    *out = from_fr(r);
+    *out = from_fr(fold_row(index, log_height, to_fr(*beta), to_fr(*e0), to_fr(*e1)));
 }
 
 int lsp_log_quotient_degree(const int32_t* air, size_t air_len, int32_t public_degree, uint32_t* log_q) {

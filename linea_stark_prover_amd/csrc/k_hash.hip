@@ -82,29 +82,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LSP_P2_ROWS
 }
 
 template <uint32_t D, int LANES>
-__global__ __launch_bounds__(256) void k_fold_hash(FoldSpec f, size_t nleaves, Fr* __restrict__ out,
-                                                   const F29* __restrict__ rc, uint32_t rf, uint32_t rp) {
-    __shared__ uint4 qt[3 * F29_QTAB_N];  // f29_reduce_qt's table
-    f29_qtab_init(qt);
-    __syncthreads();
-    const size_t j = gtid() / LANES;
-    if (j >= nleaves) return;
-    Fr e[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const size_t i = 2 * j + k;
-        const Fr p = fr_mul(f.half_beta, pow2l(f.tab, f.L1, brev_bits(f.i0 + i, f.logm)));
-        e[k] = fr_add(fr_mul(fr_add(f.half, p), f.v[2 * i]), fr_mul(fr_sub(f.half, p), f.v[2 * i + 1]));
-    }
-    if ((threadIdx.x & (LANES - 1)) == 0) {
-        f.vout[2 * j] = e[0];
-        f.vout[2 * j + 1] = e[1];
-    }
-    const Fr d = sponge_f29<D, LANES>([&](uint32_t k) { return e[k]; }, 2, rc, rf, rp, qt);
-    if ((threadIdx.x & (LANES - 1)) == 0) out[j] = d;
-}
-
-template <uint32_t D, int LANES>
 __global__ __launch_bounds__(256) void k_merkle_level(const Fr* __restrict__ src, Fr* __restrict__ dst, size_t nout,
                                                       const F29* __restrict__ rc, uint32_t rf, uint32_t rp) {
     // the narrow forms are one permutation's latency per level, the critical
@@ -245,18 +222,6 @@ hipError_t launch_hash_rows(const MatList& m, size_t nrows, Fr* out, const F29* 
             hipLaunchKernelGGL((k_hash_rows_multi<decltype(d)::value, decltype(ln)::value>), dim3(blocks), dim3(bs), 0,
                                st, m, nrows, out, rc, L.rounds_f, L.rounds_p);
         });
-    return hipGetLastError();
-}
-
-hipError_t launch_fold_hash(const FoldSpec& f, size_t nleaves, Fr* out, const F29* rc, P2Layout L, hipStream_t st) {
-    if (!nleaves) return hipSuccess;
-    const int lanes = lanes_for(nleaves);
-    unsigned blocks, bs;
-    state_grid(nleaves, lanes, blocks, bs);
-    p2_dispatch(L, lanes, [&](auto d, auto ln) {
-        hipLaunchKernelGGL((k_fold_hash<decltype(d)::value, decltype(ln)::value>), dim3(blocks), dim3(bs), 0, st, f,
-                           nleaves, out, rc, L.rounds_f, L.rounds_p);
-    });
     return hipGetLastError();
 }
 

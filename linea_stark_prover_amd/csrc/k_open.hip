@@ -1,7 +1,6 @@
 // TwoAdicFriPcs::open building blocks ([EXT p3-fri]): inverse denominators
 // 1/(z - GEN w_N^bitrev(i)), barycentric opened values (interpolate_coset),
-// the "reduce rows" accumulation, and the FRI fold
-// (TwoAdicFriGenericConfig::fold_matrix).
+// and the "reduce rows" accumulation.  (The FRI fold: k_fri.hip.)
 #include "fr29.hpp"
 #include "k_common.hpp"
 #include "kernels.hpp"
@@ -259,15 +258,6 @@ __global__ __launch_bounds__(256) void k_reduce_matrix(const Fr* __restrict__ M,
         acc = fr_add(acc, fr_mul(fr_sub(offys[p], fr_mul(off[p], rr)), inv[(size_t)p * n + i]));
     ro[i] = acc;
 }
-
-__global__ __launch_bounds__(256) void k_fri_fold(const Fr* __restrict__ v, size_t m, Fr half, Fr half_beta,
-                                                  const Fr* __restrict__ tab, uint32_t L1, uint32_t logm,
-                                                  uint64_t i0, Fr* __restrict__ out) {
-    const size_t i = gtid();
-    if (i >= m) return;
-    const Fr p = fr_mul(half_beta, pow2l(tab, L1, brev_bits(i0 + i, logm)));
-    out[i] = fr_add(fr_mul(fr_add(half, p), v[2 * i]), fr_mul(fr_sub(half, p), v[2 * i + 1]));
-}
 }  // namespace
 
 hipError_t launch_open_denoms(Fr z, Fr gen, const Fr* tabN, uint32_t L1, uint32_t logN, size_t n, Fr* den,
@@ -325,18 +315,6 @@ hipError_t launch_reduce_matrix(const Fr* M, size_t n, uint32_t w, const Fr* apw
                                 const Fr* off, const Fr* offys, Fr* ro, hipStream_t st) {
     hipLaunchKernelGGL(k_reduce_matrix, dim3(nblocks(n, 256)), dim3(256), 0, st, M, n, w, apw, npts, inv, off, offys,
                        ro);
-    return hipGetLastError();
-}
-
-hipError_t launch_fri_fold(const Fr* v, size_t m, Fr half, Fr half_beta, const Fr* tab, uint32_t L1, Fr* out,
-                           hipStream_t st, uint64_t i0, int logm) {
-    uint32_t lg = 0;
-    if (logm >= 0)
-        lg = (uint32_t)logm;
-    else
-        while ((1ull << lg) < m) ++lg;
-    hipLaunchKernelGGL(k_fri_fold, dim3(nblocks(m, 256)), dim3(256), 0, st, v, m, half, half_beta, tab, L1, lg, i0,
-                       out);
     return hipGetLastError();
 }
 

@@ -104,19 +104,6 @@ inline MatList one_mat(const Fr* p, uint32_t w) {
 hipError_t launch_rc_to_f29(const Fr* rc, F29* rc29, uint32_t n, hipStream_t st);
 hipError_t launch_permute(Fr* states, size_t n, const F29* rc29, P2Layout L, hipStream_t st);
 // out[i] = hash_iter(concat of row i of every matrix in `m`)
-// FRI fold of the previous round fused into this round's leaf hashing: the
-// folded vector v' (2 n values) is written to `vout` and leaf j = hash_iter(
-// v'[2j], v'[2j+1]) to `out`, with v'[i] = (half + p_i) v[2i] + (half - p_i) v[2i+1],
-// p_i = half_beta * tab^bitrev_logm(i0 + i) (launch_fri_fold's formula)
-struct FoldSpec {
-    const Fr* v;      // the previous round's vector (this rank's slice)
-    Fr* vout;         // where the folded vector goes
-    Fr half, half_beta;
-    const Fr* tab;    // two-level table of w_{2M}^-1
-    uint32_t L1, logm;
-    uint64_t i0;
-};
-hipError_t launch_fold_hash(const FoldSpec& f, size_t nleaves, Fr* out, const F29* rc, P2Layout L, hipStream_t st);
 hipError_t launch_hash_rows(const MatList& m, size_t nrows, Fr* out, const F29* rc29, P2Layout L, hipStream_t st);
 // dst[i] = compress(src[2i], src[2i+1]) for i < nout
 hipError_t launch_merkle_level(const Fr* src, Fr* dst, size_t nout, const F29* rc29, P2Layout L, hipStream_t st);
@@ -138,16 +125,28 @@ hipError_t launch_merkle_levels(Fr* layers, size_t nleaves, size_t stop_len, con
 hipError_t launch_merkle_inject(const Fr* src, const Fr* inj, Fr* dst, size_t nout, const F29* rc29, P2Layout L,
                                 hipStream_t st);
 
-// ------------------------------------------------------ k_fri_mixed.hip
-// FRI over inputs of unequal heights (U15): launch_fold_hash with the roll-in
-// fused.  v'[i] = fold(v)[i] + add[i] for i < 2 nleaves (add: the
-// reduced-opening vector as long as v', or nullptr) goes to f.vout and leaf
-// j = hash_iter(v'[2j], v'[2j+1]) to out, in the lane form a plain leaf batch
-// of nleaves takes
-hipError_t launch_fold_add_hash(const FoldSpec& f, const Fr* add, size_t nleaves, Fr* out, const F29* rc29, P2Layout L,
-                                hipStream_t st);
-// f.vout[i] = fold(v)[i] + add[i] for i < m (add nullable): the last fold, which no leaf kernel follows
-hipError_t launch_fri_fold_add(const FoldSpec& f, const Fr* add, size_t m, hipStream_t st);
+// ------------------------------------------------------------ k_fri.hip
+// One FRI fold (TwoAdicFriGenericConfig::fold_matrix) of a vector of global
+// folded length 2^logm, for the outputs from global index i0 on (a rank's slice):
+// vout[i] = (half + p_i) v[2i] + (half - p_i) v[2i+1] + add[i],
+// p_i = half_beta * tab^bitrev_logm(i0 + i).  add: the roll-in of FRI over inputs
+// of unequal heights (U15) -- the reduced-opening vector as long as vout,
+// already offset to this slice -- or nullptr.
+struct FoldSpec {
+    const Fr* v;      // the round's input (this rank's slice)
+    Fr* vout;         // where the folded vector goes
+    Fr half, half_beta;
+    const Fr* tab;    // two-level table of w_{2M}^-1, M = 2^logm
+    uint32_t L1, logm;
+    uint64_t i0;
+    const Fr* add;
+};
+// the fold fused into the next round's leaf hashing: 2 nleaves outputs to
+// f.vout and leaf j = hash_iter(vout[2j], vout[2j+1]) to out, in the lane form
+// a plain leaf batch of nleaves takes
+hipError_t launch_fold_hash(const FoldSpec& f, size_t nleaves, Fr* out, const F29* rc29, P2Layout L, hipStream_t st);
+// m outputs to f.vout: a fold no leaf kernel follows
+hipError_t launch_fri_fold(const FoldSpec& f, size_t m, hipStream_t st);
 
 // --------------------------------------------------------- k_field.hip
 // out[i] = 1/in[i] (0 -> 0: a zero input leaves the other outputs as they
@@ -369,16 +368,11 @@ unsigned bounds_fault_k_open();
 unsigned bounds_fault_k_witness();
 unsigned bounds_fault_k_check();
 unsigned bounds_fault_k_merkle_inject();
-unsigned bounds_fault_k_fri_mixed();
+unsigned bounds_fault_k_fri();
 #endif
 // one matrix opened at npts points (the generic reduce of TwoAdicFriPcs::open):
 // ro[i] += sum_p (offys[p] - off[p] * sum_c apw[c] M[i][c]) * inv[p*n + i]
 hipError_t launch_reduce_matrix(const Fr* M, size_t n, uint32_t w, const Fr* apw, uint32_t npts, const Fr* inv,
                                 const Fr* off, const Fr* offys, Fr* ro, hipStream_t st);
-// FRI fold of v (2m values) -> out (m values); tab: two-level table of w_{2M}^-1
-// where M = 2^logm is the whole folded length (logm < 0: M = m) and v holds
-// the pairs from global pair index i0 on (a shard of the vector).
-hipError_t launch_fri_fold(const Fr* v, size_t m, Fr half, Fr half_beta, const Fr* tab, uint32_t L1,
-                           Fr* out, hipStream_t st, uint64_t i0 = 0, int logm = -1);
 
 }  // namespace lsp

@@ -207,21 +207,23 @@ static void spin_until(hipEvent_t ev) {
     LSP_HIP(q);
 }
 
-Fr commit_device(lsp_ctx* ctx, const MatList& m, size_t height, Fr* layers, const FoldSpec* fold,
+size_t host_tree_top(const lsp_ctx* ctx) {
+    size_t top = ctx->host_tree_top;
+    if (g_active_proofs.load(std::memory_order_relaxed) > 1) top = std::min(top, SHARED_HOST_TREE_TOP);
+    return env_size("LSP_HOST_TREE_TOP", top);
+}
+
+Fr commit_device(lsp_ctx* ctx, const MatList& m, size_t height, Fr* layers, size_t top, const FoldSpec* fold,
                  const std::function<void(hipEvent_t)>* side) {
     hipStream_t st = ctx->stream;
     using clk = host_clock;
     const auto tt0 = clk::now();
     auto t_launched = tt0, t_near = tt0;
-    size_t top = ctx->host_tree_top;
-    if (g_active_proofs.load(std::memory_order_relaxed) > 1) top = std::min(top, SHARED_HOST_TREE_TOP);
-    if (const char* e = std::getenv("LSP_HOST_TREE_TOP")) top = std::strtoull(e, nullptr, 10);
     HostPool& pool = ctx->host_pool();
     size_t off = 0, len = height;
     if (fold && height <= top && height > 1) {
         // a short vector: materialise the fold, then the host path below hashes it
-        LSP_HIP(launch_fri_fold(fold->v, 2 * height, fold->half, fold->half_beta, fold->tab, fold->L1, fold->vout, st,
-                                fold->i0, (int)fold->logm));
+        LSP_HIP(launch_fri_fold(*fold, 2 * height, st));
         fold = nullptr;
     }
     const bool leaves_on_host = height <= top && m.n == 1 && height > 1;

@@ -3,16 +3,18 @@
 // one reduced-opening vector per LDE height, a FRI commit phase that rolls each
 // shorter vector in where the lengths meet, the queries) and the host
 // verifier, with the proof's wire format "LSPPCS01" (DESIGN.md section 9).
-// Built on the stage drivers the prover runs (stages.cpp, merkle_mixed.cpp);
-// the prover itself (prove.cpp) is not involved.  Every FRI round runs on the
-// device: no host tail and no host tree top on this path.
+// Built on the stage drivers the prover runs (stages.cpp, merkle_mixed.cpp) and
+// on its FRI (fri.cpp).  Every FRI round runs on the device: no host tail and
+// no host tree top on this path (the commit phase's policy values are 0 here).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <map>
 
+#include "comm.hpp"
 #include "host.hpp"
 #include "prove_internal.hpp"
+#include "wire.hpp"
 
 lsp_challenger::lsp_challenger(const lsp_ctx* ctx) : p2(ctx->p2), ch(&p2, ctx->transcript.mont_bits) {}
 
@@ -92,32 +94,10 @@ std::unique_ptr<lsp_tree> pcs_commit(lsp_ctx* ctx, const lsp_fr* const* mats, co
 }
 
 // ----------------------------------------------------------------- open
-namespace {
-// final poly: bit-reverse, IDFT (naive: at most 2^(log_blowup + log_final_poly_len) values), truncate
-std::vector<Fr> final_poly_of(const std::vector<Fr>& fin, size_t flen) {
-    const size_t n = fin.size();
-    const uint32_t lgl = log2_exact(n);
-    const Fr winv = host_inv_cached(host_two_adic_generator(lgl)), linv = host_inv_cached(fr_from_u64(n));
-    std::vector<Fr> out;
-    for (size_t k = 0; k < n; ++k) {
-        Fr acc = fr_zero(), p = fr_one();
-        const Fr wk = fr_pow_u64(winv, k);
-        for (size_t j = 0; j < n; ++j) {
-            acc = fr_add(acc, fr_mul(fin[host_bitrev(j, lgl)], p));
-            p = fr_mul(p, wk);
-        }
-        acc = fr_mul(acc, linv);
-        if (k < flen)
-            out.push_back(acc);
-        else
-            LSP_REQUIRE(fr_is_zero(acc), LSP_E_STATE, "FRI final polynomial degree too high");
-    }
-    return out;
-}
-}  // namespace
-
 std::unique_ptr<lsp_pcs_proof> pcs_open(lsp_ctx* ctx, const lsp_tree* const* trees, PcsRounds& R, Challenger& ch) {
     hipStream_t st = ctx->stream;
+    const DeferTopUploads defer(ctx);
+    SoloComm solo;
     const uint32_t lb = ctx->log_blowup;
     const Fr GEN = host_generator();
     const size_t nb = R.batches.size();
@@ -223,56 +203,17 @@ std::unique_ptr<lsp_pcs_proof> pcs_open(lsp_ctx* ctx, const lsp_tree* const* tre
                                          l.ro, st));
         }
     }
-    auto input_of_len = [&](size_t len) -> const Fr* {
-        const auto it = ro.find(log2_exact(len));
-        return it == ro.end() ? nullptr : it->second;
-    };
-
-    // ---- FRI commit phase: per round the tree of the vector's pairs -- the
-    // previous round's fold and roll-in fused into its leaves --, the root into
-    // the transcript, beta out of it, and this round's fold left pending
-    struct Round {
-        const Fr* vec;
-        const Fr* tree;
-        size_t ml;
-    };
-    std::vector<Round> rounds;
-    const size_t nmax = (size_t)1 << R.log_nmax, final_len = (size_t)1 << (lb + ctx->log_final_poly_len);
-    Fr* fv = ctx->fbuf("pcs_fvec", nmax);  // the folded vectors, back to back
-    Fr* ftree = ctx->fbuf("pcs_ftree", 2 * nmax);
-    const Fr* cur = ro.at(R.log_nmax);
-    size_t len = nmax, vo = 0, to = 0;
-    FoldSpec pend{};
-    while (len > final_len) {
-        const size_t ml = len / 2;
-        Fr* tree = ftree + to;
-        if (rounds.empty())
-            LSP_HIP(launch_hash_rows(one_mat(cur, 2), ml, tree, ctx->rc29_dev, ctx->p2.L, st));
-        else
-            LSP_HIP(launch_fold_add_hash(pend, input_of_len(len), ml, tree, ctx->rc29_dev, ctx->p2.L, st));
-        LSP_HIP(launch_merkle_tree(tree, ml, ctx->rc29_dev, ctx->p2.L, st));
-        const Fr root = d2h_fr(ctx, tree + TreeLayout{ml}.root());
-        proof->roots.push_back(root);
-        ch.observe(root);
-        const Fr beta = ch.sample();
-        pend = fold_spec(ctx, log2_exact(ml), 0, beta);
-        pend.v = cur;
-        pend.vout = fv + vo;
-        rounds.push_back({cur, tree, ml});
-        cur = fv + vo;
-        vo += ml;
-        to += TreeLayout{ml}.size();
-        len = ml;
-    }
-    LSP_HIP(launch_fri_fold_add(pend, input_of_len(len), len, st));  // the fold no leaf kernel follows
-    {
-        std::vector<Fr> fin(len);
-        Fr* hf = (Fr*)ctx->hbuf("pcs_final_h", len * sizeof(Fr));
-        LSP_HIP(hipMemcpyAsync(hf, cur, len * sizeof(Fr), hipMemcpyDeviceToHost, st));
-        LSP_HIP(hipStreamSynchronize(st));
-        std::copy(hf, hf + len, fin.begin());
-        proof->final_poly = final_poly_of(fin, (size_t)1 << ctx->log_final_poly_len);
-    }
+    // ---- FRI commit phase (fri.cpp): each shorter vector rolls in where the
+    // lengths meet; round 0's input is the tallest vector, the folds go to pcs_fvec
+    const size_t nmax = (size_t)1 << R.log_nmax;
+    FriCommit fri(
+        ctx, solo, ro.at(R.log_nmax), ctx->fbuf("pcs_fvec", nmax), nmax, proof->roots,
+        [&](size_t len) -> const Fr* {
+            const auto it = ro.find(log2_exact(len));
+            return it == ro.end() ? nullptr : it->second;
+        },
+        0, 0);
+    proof->final_poly = fri.final_poly(fri.commit(ch), false, false);
     if (ctx->transcript.final_poly)  // U12
         for (const Fr& c : proof->final_poly) ch.observe(c);
     proof->pow_w = fr_from_u64(grind_device(ctx, ch, ctx->pow_bits));
@@ -282,32 +223,19 @@ std::unique_ptr<lsp_pcs_proof> pcs_open(lsp_ctx* ctx, const lsp_tree* const* tre
     std::vector<size_t> idxs(nq);
     for (size_t& idx : idxs) idx = (size_t)ch.sample_bits(R.log_nmax);
     std::vector<uint64_t> ptrs;
-    auto P = [&](const Fr* p) { ptrs.push_back((uint64_t)(uintptr_t)p); };
-    auto path = [&](const Fr* layers, size_t leaves, size_t leaf) {
-        const TreeLayout lay{leaves};
-        for (uint32_t l = 0, n = lay.levels(); l < n; ++l) P(layers + lay.sibling(l, leaf));
-    };
     for (const size_t idx : idxs) {
         for (size_t b = 0; b < nb; ++b) {
             const lsp_tree& t = *trees[b];
             const size_t ib = idx >> (R.log_nmax - log2_exact(t.height));
             for (size_t k = 0; k < t.mats.size(); ++k)
-                for (size_t c = 0; c < t.widths[k]; ++c) P(t.mats[k] + t.row_of(k, ib) * t.widths[k] + c);
-            path(t.layers, t.height, ib);
+                for (size_t c = 0; c < t.widths[k]; ++c)
+                    ptrs.push_back((uint64_t)(uintptr_t)(t.mats[k] + t.row_of(k, ib) * t.widths[k] + c));
+            push_path(ptrs, t.layers, t.height, ib);
         }
-        for (size_t r = 0; r < rounds.size(); ++r) {
-            const size_t ii = idx >> r;  // index in round r's vector
-            P(rounds[r].vec + (ii ^ 1));
-            path(rounds[r].tree, rounds[r].ml, ii >> 1);
-        }
+        fri.push_query(ptrs, idx);
     }
-    // the gather reads its pointer list from pinned host memory and writes the
-    // openings into coherent pinned memory: no copy either side of the kernel
-    uint64_t* hp = (uint64_t*)ctx->hbuf("pcs_ptrs", ptrs.size() * sizeof(uint64_t));
-    std::memcpy(hp, ptrs.data(), ptrs.size() * sizeof(uint64_t));
-    Fr* got = (Fr*)ctx->hbuf("pcs_opened", ptrs.size() * sizeof(Fr), hipHostMallocCoherent);
-    LSP_HIP(launch_gather(hp, got, ptrs.size(), st));
-    LSP_HIP(hipStreamSynchronize(st));
+    flush_top_uploads(ctx);  // the gather reads the tree tops
+    const Fr* got = gather_to_host(ctx, ptrs);
     const Fr* e = got;
     proof->queries.resize(nq);
     for (lsp_pcs_proof::Query& q : proof->queries) {
@@ -322,10 +250,10 @@ std::unique_ptr<lsp_pcs_proof> pcs_open(lsp_ctx* ctx, const lsp_tree* const* tre
             q.paths[b].assign(e, e + lg);
             e += lg;
         }
-        q.fpath.resize(rounds.size());
-        for (size_t r = 0; r < rounds.size(); ++r) {
+        q.fpath.resize(fri.rounds.size());
+        for (size_t r = 0; r < fri.rounds.size(); ++r) {
             q.sib.push_back(*e++);
-            const uint32_t lg = log2_exact(rounds[r].ml);
+            const uint32_t lg = log2_exact(fri.rounds[r].ml);
             q.fpath[r].assign(e, e + lg);
             e += lg;
         }
@@ -339,76 +267,18 @@ std::unique_ptr<lsp_pcs_proof> pcs_open(lsp_ctx* ctx, const lsp_tree* const* tre
 //   | opened values [batch][matrix][point][column] | roots[rounds] | final_poly | pow_witness
 //   | per query: per batch { row elements, u32 len, path[len] }, per round { sibling, u32 len, path[len] }
 // little-endian words, elements as 32-byte little-endian canonical integers
-namespace {
-struct Writer {
-    std::vector<uint8_t>& out;
-    void u32(uint32_t x) {
-        for (int i = 0; i < 4; ++i) out.push_back((uint8_t)(x >> (8 * i)));
-    }
-    void fr(const Fr& x) {
-        const Fr c = fr_to_canonical(x);
-        for (int i = 0; i < 8; ++i)
-            for (int k = 0; k < 4; ++k) out.push_back((uint8_t)(c.v[i] >> (8 * k)));
-    }
-    void frs(const std::vector<Fr>& v) {
-        for (const Fr& x : v) fr(x);
-    }
-    void path(const std::vector<Fr>& v) {
-        u32((uint32_t)v.size());
-        frs(v);
-    }
-};
-
-// bounds-checked reader: every overrun or non-canonical element sets `bad`
-struct Reader {
-    const uint8_t* b;
-    size_t n, off = 0;
-    bool bad = false;
-    size_t left() const { return n - off; }
-    uint32_t u32() {
-        if (bad || left() < 4) {
-            bad = true;
-            return 0;
-        }
-        uint32_t x = 0;
-        for (int i = 0; i < 4; ++i) x |= (uint32_t)b[off + i] << (8 * i);
-        off += 4;
-        return x;
-    }
-    Fr fr() {
-        Fr c = fr_zero();
-        if (bad || left() < 32) {
-            bad = true;
-            return c;
-        }
-        for (int i = 0; i < 8; ++i) {
-            uint32_t x = 0;
-            for (int k = 0; k < 4; ++k) x |= (uint32_t)b[off + 4 * i + k] << (8 * k);
-            c.v[i] = x;
-        }
-        off += 32;
-        if (!fr_words_lt_mod(c)) {
-            bad = true;
-            return fr_zero();
-        }
-        return fr_from_canonical(c);
-    }
-    // cnt elements, refusing counts the remaining bytes cannot hold (nothing is sized before that)
-    void frs(std::vector<Fr>& v, uint64_t cnt) {
-        if (bad || cnt > left() / 32) {
-            bad = true;
-            return;
-        }
-        v.resize((size_t)cnt);
-        for (Fr& x : v) x = fr();
-    }
-};
-}  // namespace
-
 std::vector<uint8_t> pcs_serialize(const lsp_pcs_proof& p) {
-    std::vector<uint8_t> out(8);
+    size_t nu32 = 4, nfr = p.ys.size() + p.roots.size() + p.final_poly.size() + 1;
+    for (const auto& B : p.shape) nu32 += 1 + 2 * B.size();
+    for (const auto& q : p.queries) {
+        nu32 += p.shape.size() + p.roots.size();
+        nfr += p.roots.size();
+        for (size_t b = 0; b < p.shape.size(); ++b) nfr += q.rows[b].size() + q.paths[b].size();
+        for (size_t r = 0; r < p.roots.size(); ++r) nfr += q.fpath[r].size();
+    }
+    std::vector<uint8_t> out(8 + 4 * nu32 + 32 * nfr);
     std::memcpy(out.data(), "LSPPCS01", 8);
-    Writer w{out};
+    Writer w{out.data() + 8};
     w.u32((uint32_t)p.shape.size());
     w.u32((uint32_t)p.queries.size());
     w.u32((uint32_t)p.roots.size());
@@ -434,6 +304,7 @@ std::vector<uint8_t> pcs_serialize(const lsp_pcs_proof& p) {
             w.path(q.fpath[r]);
         }
     }
+    LSP_REQUIRE(w.p == out.data() + out.size(), LSP_E_STATE, "PCS proof serialization size mismatch");
     return out;
 }
 
@@ -510,17 +381,8 @@ int pcs_verify_host(const lsp_ctx* ctx, const Fr* commits, PcsRounds& R, const u
     if (ctx->transcript.opened_values)
         for (const Fr& y : p.ys) ch.observe(y);
     const Fr alpha = ch.sample();
-    std::vector<Fr> betas(nr);
-    for (uint32_t k = 0; k < nr; ++k) {
-        ch.observe(p.roots[k]);
-        betas[k] = ch.sample();
-    }
-    if (ctx->transcript.final_poly)
-        for (const Fr& c : p.final_poly) ch.observe(c);
-    const Fr pwc = fr_to_canonical(p.pow_w);
-    for (int i = 2; i < 8; ++i)
-        if (pwc.v[i]) return 6;
-    if (!ch.check_witness(ctx->pow_bits, (uint64_t)pwc.v[0] | ((uint64_t)pwc.v[1] << 32))) return 7;
+    std::vector<Fr> betas;
+    if (const int bad = fri_replay(ch, ctx, p.roots, p.final_poly, p.pow_w, betas)) return bad;
 
     // per (matrix, point): the running power of its height and the reduced opened values times it
     size_t maxw = 0;
@@ -587,30 +449,15 @@ int pcs_verify_host(const lsp_ctx* ctx, const Fr* commits, PcsRounds& R, const u
                 row += m.width;
             }
         }
-        Fr folded = fr_zero();
-        size_t index = idx;
-        for (uint32_t k = 0; k < nr; ++k) {
-            const uint32_t log_folded = lmax - 1 - k;
-            const auto it = ro.find(log_folded + 1);  // the roll-in: plain addition
-            if (it != ro.end()) folded = fr_add(folded, it->second);
-            Fr ev[2];
-            ev[(index ^ 1) & 1] = q.sib[k];
-            ev[index & 1] = folded;
-            if (q.fpath[k].size() != log_folded) return 10;
-            const Fr got = merkle_path_root(
-                ctx->p2, ctx->p2.hash(ev, 2), index >> 1, log_folded, [&](uint32_t l) { return q.fpath[k][l]; },
-                no_injection);
-            if (!fr_eq(got, p.roots[k])) return 10;
-            index >>= 1;
-            // TwoAdicFriGenericConfig::fold_row
-            const Fr s0 = fr_pow_u64(host_two_adic_generator(log_folded + 1), host_bitrev(index, log_folded));
-            folded = fr_add(ev[0], fr_mul(fr_mul(fr_sub(betas[k], s0), fr_sub(ev[1], ev[0])),
-                                          fr_inv(fr_sub(fr_neg(s0), s0))));
-        }
-        const Fr xf = fr_pow_u64(host_two_adic_generator(lmax - nr), host_bitrev(index, lmax - nr));
-        Fr ev = fr_zero();
-        for (size_t k = flen; k-- > 0;) ev = fr_add(fr_mul(ev, xf), p.final_poly[k]);
-        if (!fr_eq(ev, folded)) return 11;
+        const int bad = fri_check_query(
+            ctx->p2, p.roots, betas, p.final_poly, lmax, idx,
+            [&](uint32_t l) -> const Fr* {
+                const auto it = ro.find(l);
+                return it == ro.end() ? nullptr : &it->second;
+            },
+            [&](uint32_t k) { return q.sib[k]; }, [&](uint32_t k) { return (uint32_t)q.fpath[k].size(); },
+            [&](uint32_t k, uint32_t l) { return q.fpath[k][l]; });
+        if (bad) return bad;
     }
     return 0;
 }

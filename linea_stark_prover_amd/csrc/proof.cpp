@@ -18,73 +18,9 @@
 #include <mutex>
 
 #include "prove_internal.hpp"
+#include "wire.hpp"
 
 namespace lsp {
-
-// little-endian words and canonical field elements, written in one pass into a
-// buffer sized up front
-namespace {
-struct Writer {
-    uint8_t* p;
-    void u32(uint32_t x) {
-        for (int i = 0; i < 4; ++i) *p++ = (uint8_t)(x >> (8 * i));
-    }
-    void fr(const Fr& x) {
-        // Montgomery form -> integer: one Montgomery reduction (a product by 1
-        // without the product rows) on the 4 x 64-bit host arithmetic
-        const Fr c = hp64::to_canonical(hp64::redc(hp64::from(x)));
-        std::memcpy(p, c.v, 32);  // 32-bit words little-endian (x86-64 host)
-        p += 32;
-    }
-    void frs(const std::vector<Fr>& v) {
-        for (auto& x : v) fr(x);
-    }
-};
-
-// bounds-checked reader: every overrun or non-canonical element sets `bad`
-struct Reader {
-    const uint8_t* b;
-    size_t n, off = 0;
-    bool bad = false;
-    uint32_t u32() {
-        if (bad || n - off < 4) {
-            bad = true;
-            return 0;
-        }
-        uint32_t x = 0;
-        for (int i = 0; i < 4; ++i) x |= (uint32_t)b[off + i] << (8 * i);
-        off += 4;
-        return x;
-    }
-    Fr fr() {
-        Fr c = fr_zero();
-        if (bad || n - off < 32) {
-            bad = true;
-            return c;
-        }
-        for (int i = 0; i < 8; ++i) {
-            uint32_t x = 0;
-            for (int k = 0; k < 4; ++k) x |= (uint32_t)b[off + 4 * i + k] << (8 * k);
-            c.v[i] = x;
-        }
-        off += 32;
-        if (!fr_words_lt_mod(c)) {
-            bad = true;
-            return fr_zero();
-        }
-        return fr_from_canonical(c);
-    }
-    // n elements, refusing counts the remaining bytes cannot hold (no huge allocations)
-    void frs(std::vector<Fr>& v, size_t cnt) {
-        if (bad || cnt > (n - off) / 32) {
-            bad = true;
-            return;
-        }
-        v.resize(cnt);
-        for (auto& x : v) x = fr();
-    }
-};
-}  // namespace
 
 namespace {
 struct Recycler {

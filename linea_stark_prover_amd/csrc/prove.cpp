@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <optional>
 
 #include "comm.hpp"
 #include "host.hpp"
@@ -221,14 +222,6 @@ Shard shard_geometry(const lsp_ctx* ctx, const Comm& comm, size_t h, size_t w, c
     return s;
 }
 
-struct FriRound {
-    const Fr* vec;   // this rank's copy of the round's input (its slice when sharded)
-    const Fr* tree;  // layers of this rank's (sub)tree
-    size_t ml;       // leaves of that (sub)tree
-    bool sharded;
-    std::vector<std::vector<Fr>> top;
-};
-
 // One proof: the state its phases hand on, and the phases in the order
 // prove_shard calls them.  The transcript is prove_shard's; only the per-round
 // (root, beta) pairs of the FRI commit phase are observed and sampled here.
@@ -269,19 +262,10 @@ struct Prover {
     const Fr *plde = nullptr, *play = nullptr;
     size_t wp = 0;
     Fr proot;
-    // FRI: this rank's slice of round r's input (length (N >> r) / G), back to
-    // back in fvec; the commit phase's cursor (fv + vo: the current round's
-    // input of global length len, ftree + to: its tree) and the fold it owes
-    Fr *fvec = nullptr, *ftree = nullptr, *fv = nullptr;
-    size_t len = 0, vo = 0, to = 0;
-    bool sharded = false;
-    size_t fri_shard_min = 0;  // shortest slice worth a collective per round
-    const Fr half = host_inv_cached(fr_from_u64(2));
-    // round r's fold (by beta_r) runs fused into round r+1's leaf hashing
-    FoldSpec pend{};
-    size_t pend_m = 0;  // folded values (this rank's slice)
-    bool pending = false;
-    std::vector<FriRound> rounds;
+    // FRI: round 0's input, this rank's slice, at fvec[0, S) with the fold area
+    // behind it; the commit phase (fri.cpp)
+    Fr* fvec = nullptr;
+    std::optional<FriCommit> fri;
     // LSP_TIME_TOPS
     host_clock::time_point t_entry, t_lde_issued, q0, q1, q2, q3;
 
@@ -325,7 +309,8 @@ struct Prover {
         tlay = ctx->fbuf("t_tree", TreeLayout{s.S}.size());
         T.begin("merkle tree");
         proof->troot = shard_root(
-            ctx, comm, commit_device(ctx, one_mat(lde, (uint32_t)s.w), s.S, tlay, nullptr, early ? &side_fn : nullptr),
+            ctx, comm, commit_device(ctx, one_mat(lde, (uint32_t)s.w), s.S, tlay, host_tree_top(ctx), nullptr,
+                               early ? &side_fn : nullptr),
             ttop, "trace subtree roots");
         T.end("merkle tree");
         T.end("commit to trace data");
@@ -494,7 +479,8 @@ struct Prover {
         }
         T.end("coset_lde_batch (quotient)");
         qlay = ctx->fbuf("q_tree", TreeLayout{s.S}.size());
-        proof->qroot = shard_root(ctx, comm, commit_device(ctx, one_mat(qlde, (uint32_t)q), s.S, qlay), qtop,
+        proof->qroot = shard_root(ctx, comm,
+                                  commit_device(ctx, one_mat(qlde, (uint32_t)q), s.S, qlay, host_tree_top(ctx)), qtop,
                                   "quotient subtree roots");
         T.end("commit to quotient poly chunks");
     }
@@ -659,206 +645,16 @@ struct Prover {
         LSP_HIP(launch_reduce_prep(pa, st));
     }
 
-    // ---- FRI commit phase: per round the tree of the vector's pairs, its root
-    // into the transcript, beta out of it, the fold.  Returns the final vector.
+    // ---- FRI commit phase (fri.cpp): no roll-in; the host takes the tree tops
+    // and the last rounds.  Returns the final vector.
     std::vector<Fr> fri_commit(Challenger& ch) {
         T.begin("FRI prover");
         T.begin("commit phase");
-        const size_t final_len = (size_t)1 << (s.lb + ctx->log_final_poly_len);
-        fri_shard_min = (size_t)1 << 12;  // (tests lower it to shard every round)
-        if (const char* e = std::getenv("LSP_FRI_SHARD_MIN"))
-            fri_shard_min = std::max<size_t>(1, std::strtoull(e, nullptr, 10));
-        ftree = ctx->fbuf("f_tree", 2 * s.S + 2 * (size_t)s.G * fri_shard_min);
-        fv = fvec;
-        len = s.N;
-        vo = to = 0;
-        sharded = s.G > 1;
-        size_t host_tail = ctx->fri_host_tail;
-        if (const char* e = std::getenv("LSP_FRI_HOST_TAIL")) host_tail = std::strtoull(e, nullptr, 10);
-        const Fr* hfin = nullptr;  // the final vector, when the host ran the last rounds
-        while (len > final_len) {
-            if (sharded && (len >> s.b) < 2 * fri_shard_min) {
-                flush_fold();  // the gathered vector must exist
-                replicate();
-            }
-            if (!sharded && len / 2 <= host_tail) {
-                hfin = fri_host_tail(ch, final_len);
-                break;
-            }
-            fri_device_round(ch);
-        }
-        flush_fold();
-        if (sharded) replicate();
-        std::vector<Fr> fin(len);
-        if (hfin)
-            std::copy(hfin, hfin + len, fin.begin());
-        else {
-            Fr* hf = (Fr*)ctx->hbuf("f_final_h", len * sizeof(Fr));
-            LSP_HIP(hipMemcpyAsync(hf, fv + vo, len * sizeof(Fr), hipMemcpyDeviceToHost, st));
-            LSP_HIP(hipStreamSynchronize(st));
-            std::copy(hf, hf + len, fin.begin());
-        }
+        fri.emplace(ctx, comm, fvec, fvec + s.S, s.N, proof->roots, [](size_t) { return (const Fr*)nullptr; },
+                    host_tree_top(ctx), ctx->fri_host_tail);
+        std::vector<Fr> fin = fri->commit(ch);
         T.end("commit phase");
         return fin;
-    }
-
-    void replicate() {  // gather the short vector to every rank
-        const size_t loc = len >> s.b;
-        Fr* rep = ctx->fbuf("f_rep", 2 * len);
-        comm.allgather(ctx, fv + vo, rep, loc * sizeof(Fr), "FRI vector");
-        fv = rep;
-        vo = 0;
-        sharded = false;
-    }
-
-    void flush_fold() {  // the fold no later leaf kernel will run
-        if (!pending) return;
-        fri_fold(ctx, pend, pend_m);
-        pending = false;
-    }
-
-    // one round on the device: the tree (with the previous round's fold fused
-    // into its leaves), then this round's fold left pending
-    void fri_device_round(Challenger& ch) {
-        const size_t m = len / 2, ml = sharded ? (m >> s.b) : m;
-        FriRound R;
-        R.vec = fv + vo;
-        R.tree = ftree + to;
-        R.ml = ml;
-        R.sharded = sharded;
-        const Fr lroot = commit_device(ctx, one_mat(fv + vo, 2), ml, ftree + to, pending ? &pend : nullptr);
-        pending = false;
-        const Fr root = sharded ? shard_root(ctx, comm, lroot, R.top, "FRI subtree roots") : lroot;
-        proof->roots.push_back(root);
-        ch.observe(root);
-        const Fr beta = ch.sample();
-        pend = fold_spec(ctx, log2_exact(m), sharded ? (uint64_t)s.g * ml : 0, beta);
-        pend.v = fv + vo;
-        pend.vout = fv + vo + 2 * ml;
-        pend_m = ml;
-        pending = true;
-        rounds.push_back(std::move(R));
-        vo += 2 * ml;
-        to += TreeLayout{ml}.size();
-        len = m;
-    }
-
-    // The last rounds wholly on the host: their trees are a few thousand
-    // permutations in a chain of short levels (~58 us each on the GPU, a few
-    // us on the host pool).  One download of the vector; per round the host
-    // hashes the tree, samples beta and folds; the layers and folded vectors
-    // go back asynchronously for the query openings, which gather on the device.
-    // Returns the final vector (in the pinned "fri_tail" buffer).
-    const Fr* fri_host_tail(Challenger& ch, size_t final_len) {
-        flush_fold();
-        const auto th0 = host_clock::now();
-        size_t hn = final_len, ht = 0;
-        for (size_t l = len; l > final_len; l /= 2) {
-            hn += l;
-            ht += l - 1;
-        }
-        Fr* hv = (Fr*)ctx->hbuf("fri_tail", (hn + ht) * sizeof(Fr));
-        Fr* htr = hv + hn;
-        LSP_HIP(hipMemcpyAsync(hv, fv + vo, len * sizeof(Fr), hipMemcpyDeviceToHost, st));
-        LSP_HIP(hipStreamSynchronize(st));
-        const auto th1 = host_clock::now();
-        const size_t rounds_gpu = rounds.size();
-        size_t hvo = 0, hto = 0;
-        const size_t to0 = to, vo0 = vo, len0 = len;
-        while (len > final_len) {
-            const size_t end = fri_host_round(ch, hv + hvo, htr + hto);
-            hvo += len;
-            vo += len;
-            hto += end;
-            to += end;
-            len /= 2;
-        }
-        // every round's layers and folded vector back to the device (for the
-        // query gather): both are contiguous, so two copies instead of two per round
-        LSP_HIP(hipMemcpyAsync(ftree + to0, htr, (to - to0) * sizeof(Fr), hipMemcpyHostToDevice, st));
-        LSP_HIP(hipMemcpyAsync(fv + vo0 + len0, hv + len0, (hvo + len - len0) * sizeof(Fr), hipMemcpyHostToDevice, st));
-        if (time_tops())
-            std::fprintf(stderr, "[fri tail] %zu rounds on the host: %.1f us (download %.1f us)\n",
-                         rounds.size() - rounds_gpu, us(th0, host_clock::now()), us(th0, th1));
-        return hv + hvo;
-    }
-
-    // one host round over v[0, len): its tree into lay (returns the layers'
-    // length), the root and beta, the folded vector to v + len
-    size_t fri_host_round(Challenger& ch, Fr* v, Fr* lay) {
-        const size_t m = len / 2;
-        const uint32_t logm = log2_exact(m);
-        const auto tr0 = host_clock::now();
-        // leaves (a 2-element leaf's hash_iter is compress, A4/A5) and levels in one pass
-        auto tr1 = tr0;
-        const size_t end = host_levels(ctx, lay, m, &tr1, v);
-        const auto tr2 = host_clock::now();
-        FriRound R;
-        R.vec = fv + vo;
-        R.tree = ftree + to;
-        R.ml = m;
-        R.sharded = false;
-        const Fr root = lay[end - 1];
-        proof->roots.push_back(root);
-        ch.observe(root);
-        const Fr hb = fr_mul(ch.sample(), half);
-        std::vector<Fr>& tw = ctx->fold_tw[logm];  // g^-bitrev(i), g = w_{2m}
-        if (tw.size() != m) {
-            const Fr ginv = host_inv_cached(host_two_adic_generator(logm + 1));
-            std::vector<Fr> pw(m);
-            pw[0] = one;
-            for (size_t j = 1; j < m; ++j) pw[j] = fr_mul(pw[j - 1], ginv);
-            tw.resize(m);
-            for (size_t i = 0; i < m; ++i) tw[i] = pw[host_bitrev(i, logm)];
-        }
-        Fr* out = v + len;
-        // half (v0 + v1) + hb g^-bitrev(i) (v0 - v1), in the 64-bit lazy
-        // form; short vectors on this thread (a pool round trip costs more)
-        const hp64::F hh = hp64::from(half), hbb = hp64::from(hb);
-        auto fold_blk = [&](size_t i0, size_t i1) {
-            for (size_t i = i0; i < i1; ++i) {
-                const hp64::F a = hp64::from(v[2 * i]), b = hp64::from(v[2 * i + 1]);
-                const hp64::F p = hp64::mul(hbb, hp64::from(tw[i]));
-                out[i] = hp64::to_canonical(hp64::add(hp64::mul(hh, hp64::add(a, b)), hp64::mul(p, hp64::sub(a, b))));
-            }
-        };
-        if (m <= 256)
-            fold_blk(0, m);
-        else
-            ctx->host_pool().parallel_for((m + 63) / 64,
-                                          [&](size_t blk) { fold_blk(64 * blk, std::min(m, 64 * blk + 64)); });
-        if (time_tops())
-            std::fprintf(stderr,
-                         "[fri tail round] m %5zu  leaves %6.1f  levels %6.1f  challenge+fold+copies %6.1f us\n", m,
-                         us(tr0, tr1), us(tr1, tr2), us(tr2, host_clock::now()));
-        rounds.push_back(std::move(R));
-        return end;
-    }
-
-    // final poly: bit-reverse, IDFT (naive, len <= 2^lb small), truncate
-    void final_poly(const std::vector<Fr>& fin) {
-        const size_t n = fin.size();
-        span("divide_by_height", 1, n, -1);
-        const uint32_t lgl = log2_exact(n);
-        std::vector<Fr> br(n);
-        for (size_t i = 0; i < n; ++i) br[i] = fin[host_bitrev(i, lgl)];
-        const Fr winv = host_inv_cached(host_two_adic_generator(lgl));
-        const Fr linv = host_inv_cached(fr_from_u64(n));
-        const size_t flen = (size_t)1 << ctx->log_final_poly_len;
-        for (size_t k = 0; k < n; ++k) {
-            Fr acc = fr_zero();
-            const Fr wk = fr_pow_u64(winv, k);
-            Fr p = one;
-            for (size_t j = 0; j < n; ++j) {
-                acc = fr_add(acc, fr_mul(br[j], p));
-                p = fr_mul(p, wk);
-            }
-            acc = fr_mul(acc, linv);
-            if (k < flen)
-                proof->final_poly.push_back(acc);
-            else  // (a rehearsal rank's fabricated peer data folds to no polynomial: not checked)
-                LSP_REQUIRE(fr_is_zero(acc) || comm.rehearsal(), LSP_E_STATE, "FRI final polynomial degree too high");
-        }
     }
 
     // ---- query phase: the owner of a query's row (rank idx / S) gathers the
@@ -875,7 +671,7 @@ struct Prover {
         const uint32_t nq = (uint32_t)idxs.size();
         size_t E = s.w + s.logS + s.q + s.logS;  // elements per query below the rank subtrees
         if (wp) E += wp + s.logS;                // the preprocessed row and its whole path (one rank: logS = logN)
-        for (const FriRound& R : rounds) E += 1 + log2_exact(R.ml);
+        E += fri->query_elems();
         std::vector<uint64_t> ptrs;
         std::vector<uint32_t> mine;
         query_pointers(idxs, ptrs, mine);
@@ -887,7 +683,7 @@ struct Prover {
         std::vector<Fr> slots(in_place ? 0 : (size_t)nq * E, fr_zero());
         const Fr* opened = nullptr;  // the openings of every query, (owner rank, query)-major
         if (!ptrs.empty()) {
-            const Fr* got = gather(ptrs);
+            const Fr* got = gather_to_host(ctx, ptrs);
             if (in_place)
                 opened = got;
             else
@@ -915,57 +711,23 @@ struct Prover {
             mine.push_back(qi);
             const size_t li = idx - s.row0;
             auto P = [&](const Fr* p) { ptrs.push_back((uint64_t)(uintptr_t)p); };
-            auto path = [&](const Fr* layers, size_t leaves, size_t leaf) {
-                const TreeLayout lay{leaves};
-                for (uint32_t l = 0, n = lay.levels(); l < n; ++l) P(layers + lay.sibling(l, leaf));
-            };
             for (size_t c = 0; c < w; ++c) P(lde + li * w + c);
-            path(tlay, S, li);
+            push_path(ptrs, tlay, S, li);
             for (size_t j = 0; j < q; ++j) P(qlde + li * q + j);
-            path(qlay, S, li);
+            push_path(ptrs, qlay, S, li);
             if (wp) {  // (one rank: li = idx, S = N, the tree's layers hold every level)
                 for (size_t c = 0; c < wp; ++c) P(plde + li * wp + c);
-                path(play, S, li);
+                push_path(ptrs, play, S, li);
             }
-            for (size_t r = 0; r < rounds.size(); ++r) {
-                const FriRound& R = rounds[r];
-                const size_t ii = idx >> r;                                  // global index in round r's vector
-                const size_t base = R.sharded ? (size_t)s.g * 2 * R.ml : 0;  // global index of R.vec[0]
-                P(R.vec + ((ii ^ 1) - base));
-                path(R.tree, R.ml, (ii >> 1) - base / 2);
-            }
+            fri->push_query(ptrs, idx);
         }
-    }
-
-    // the elements at ptrs, on the host
-    const Fr* gather(const std::vector<uint64_t>& ptrs) {
-        // the gather reads its pointer list from pinned host memory and writes the
-        // openings into coherent pinned memory: no copy either side of the kernel
-        // (LSP_GATHER_ZEROCOPY=0: upload, gather to HBM, download; read per call)
-        const char* zc = std::getenv("LSP_GATHER_ZEROCOPY");
-        Fr* got;
-        if (!(zc && *zc == '0')) {
-            uint64_t* hp = (uint64_t*)ctx->hbuf("g_ptrs_zc", ptrs.size() * sizeof(uint64_t));
-            std::memcpy(hp, ptrs.data(), ptrs.size() * sizeof(uint64_t));
-            got = (Fr*)ctx->hbuf("g_out_zc", ptrs.size() * sizeof(Fr), hipHostMallocCoherent);
-            LSP_HIP(launch_gather(hp, got, ptrs.size(), st));
-        } else {
-            uint64_t* dptrs = (uint64_t*)ctx->buf("g_ptrs", ptrs.size() * sizeof(uint64_t));
-            Fr* dgot = ctx->fbuf("g_out", ptrs.size());
-            ctx->h2d_async("g_ptrs_h", dptrs, ptrs.data(), ptrs.size() * sizeof(uint64_t));
-            LSP_HIP(launch_gather(dptrs, dgot, ptrs.size(), st));
-            got = (Fr*)ctx->hbuf("g_out_h", ptrs.size() * sizeof(Fr));  // pinned: no staging copy
-            LSP_HIP(hipMemcpyAsync(got, dgot, ptrs.size() * sizeof(Fr), hipMemcpyDeviceToHost, st));
-        }
-        LSP_HIP(hipStreamSynchronize(st));
-        return got;
     }
 
     // each query's record is independent: assembled (and serialized)
     // on the host pool -- ~0.1 + 0.2 ms of one thread's time at 2^19
     void query_records(const std::vector<size_t>& idxs, const Fr* opened, size_t E) {
         const size_t w = s.w, q = s.q, nq = idxs.size();
-        const uint32_t logS = s.logS, nr = (uint32_t)rounds.size();
+        const uint32_t logS = s.logS, nr = (uint32_t)fri->rounds.size();
         auto top_path = [&](const std::vector<std::vector<Fr>>& top, size_t sub, std::vector<Fr>& out) {
             for (uint32_t i = 0; i + 1 < top.size(); ++i) out.push_back(top[i][(sub >> i) ^ 1]);
         };
@@ -999,7 +761,7 @@ struct Prover {
                 e += logS;
             }
             for (uint32_t r = 0; r < nr; ++r) {
-                const FriRound& R = rounds[r];
+                const FriRound& R = fri->rounds[r];
                 qq.sib.push_back(*e++);
                 const uint32_t lg = log2_exact(R.ml);
                 std::vector<Fr>& pth = qq.fpath[r];
@@ -1086,7 +848,7 @@ lsp_proof* prove_shard(lsp_ctx* ctx, Comm& comm, const Fr* d_trace, size_t h, si
 
     P.reduce_rows(alpha_fri);
     const std::vector<Fr> fin = P.fri_commit(ch);  // per round: observe(root), beta = sample()
-    P.final_poly(fin);
+    P.proof->final_poly = P.fri->final_poly(fin, true, comm.rehearsal());
     if (TC.final_poly)  // U12
         for (const Fr& c : P.proof->final_poly) ch.observe(c);
     P.T.begin("grind for proof-of-work witness");

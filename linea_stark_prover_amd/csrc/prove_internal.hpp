@@ -1,5 +1,6 @@
 #pragma once
 #include <chrono>
+#include <cstdlib>
 #include <functional>
 #include <string>
 #include <vector>
@@ -14,6 +15,11 @@ bool time_tops();
 using host_clock = std::chrono::steady_clock;
 inline double us(host_clock::time_point a, host_clock::time_point b) {
     return std::chrono::duration<double, std::micro>(b - a).count();
+}
+// the unsigned value of environment variable `name`, or dflt when it is not set
+inline size_t env_size(const char* name, size_t dflt) {
+    const char* e = std::getenv(name);
+    return e ? (size_t)std::strtoull(e, nullptr, 10) : dflt;
 }
 // ---- lde.cpp
 // two-level power table of `base` covering exponents < 2^bits, cached in the context
@@ -50,8 +56,8 @@ struct CosetFactor {
     Fr at(const Fr& z) const { return fr_mul(fr_sub(fr_pow_u64(z, h), ch), inv_hch); }
 };
 // the FRI fold by beta of a vector of global folded length 2^logm, for the
-// pairs from global pair index i0 on (v and vout are the caller's to set);
-// fri_fold launches it for m pairs
+// pairs from global pair index i0 on (v, vout and the roll-in add are the
+// caller's to set); fri_fold launches it for m pairs
 FoldSpec fold_spec(lsp_ctx* ctx, uint32_t logm, uint64_t i0, const Fr& beta);
 void fri_fold(lsp_ctx* ctx, const FoldSpec& f, size_t m);
 // alpha^k, k < n, and a row of opened values reduced by them: sum_c apw[c] ys[c], c < w
@@ -128,7 +134,12 @@ void coset_dft_device(lsp_ctx* ctx, const Fr* d_coef, size_t h, size_t w, const 
 void coset_idft_device(lsp_ctx* ctx, const Fr* d_evals, size_t h, size_t w, const Fr& shift, Fr* d_out);
 // the pending phase events of the last proof -> ctx->timings (prove.cpp)
 void resolve_timings(lsp_ctx* ctx);
+// Merkle levels of at most this many digests run on the host: the context's
+// value, 256 while several proofs are in flight in the process, LSP_HOST_TREE_TOP
+// over both
+size_t host_tree_top(const lsp_ctx* ctx);
 // leaves + every layer into `layers` (2*height - 1); returns the root
+// top: the caller's host_tree_top (0: every level on the device)
 // fold: when set, the leaves are the pairs of the FRI fold it describes (fused
 // into the leaf kernel; m.ptr[0] receives the folded vector)
 // side (optional): called once, after the tree's launches are issued and before
@@ -136,7 +147,7 @@ void resolve_timings(lsp_ctx* ctx);
 // the leaves and the wide levels (every level of more than 2^15 digests): work
 // queued behind it on another stream fills the chip beside the narrow levels
 // and the host's tree top
-Fr commit_device(lsp_ctx* ctx, const MatList& m, size_t height, Fr* layers, const FoldSpec* fold = nullptr,
+Fr commit_device(lsp_ctx* ctx, const MatList& m, size_t height, Fr* layers, size_t top, const FoldSpec* fold = nullptr,
                  const std::function<void(hipEvent_t)>* side = nullptr);
 // Mixed-height batches (merkle_mixed.cpp; U14).  A class = the matrices of one
 // height, by the caller's indices in the caller's order; classes tallest first
@@ -161,6 +172,85 @@ bool verify_mixed_host(const lsp_ctx* ctx, const Fr& root, const std::vector<Hei
                        size_t nmats, size_t index, const lsp_fr* rows, const lsp_fr* path);
 // GrindingChallenger::grind(bits) on the device, re-checked on (and applied to) the host transcript (prove.cpp)
 uint64_t grind_device(lsp_ctx* ctx, Challenger& ch, uint32_t bits);
+// ---- fri.cpp: FRI, shared by the prover (prove.cpp) and the PCS (pcs.cpp)
+struct FriRound {
+    const Fr* vec;   // this rank's copy of the round's input (its slice when sharded)
+    const Fr* tree;  // layers of this rank's (sub)tree
+    size_t ml;       // leaves of that (sub)tree
+    bool sharded;
+    std::vector<std::vector<Fr>> top;
+};
+// The commit phase: per round the tree of the vector's pairs (the previous
+// round's fold, with any roll-in, fused into its leaves), its root into `roots`
+// and the transcript, beta out of it, and this round's fold left pending.  On
+// comm's ranks each holds a contiguous slice of the vector until a slice is
+// shorter than fri_shard_min; the last rounds run on the host once a round has
+// at most host_tail leaves and no roll-in remains.
+struct FriCommit {
+    // the reduced-opening vector of `len` elements that rolls in where the
+    // folded vector is as long (device memory), or nullptr
+    using AddOfLen = std::function<const Fr*(size_t len)>;
+    lsp_ctx* const ctx;
+    Comm& comm;
+    const uint32_t b, g;  // log2 of the ranks, this rank
+    const size_t final_len;
+    // policy, fixed here: LSP_HOST_TREE_TOP / LSP_FRI_HOST_TAIL / LSP_FRI_SHARD_MIN override the caller's values
+    const size_t host_tree_top, host_tail, fri_shard_min;
+    const AddOfLen add_of_len;
+    std::vector<Fr>& roots;
+    // the cursor: the current round's input (this rank's slice of a vector of
+    // global length len), where the next fold goes (area + ao: the folds lie
+    // back to back), the next tree (ftree + to) -- and the fold still owed:
+    // round r's fold (by beta_r) runs fused into round r+1's leaf hashing
+    const Fr* cur;
+    Fr* area;
+    Fr* ftree = nullptr;
+    size_t len, ao = 0, to = 0;
+    bool sharded;
+    FoldSpec pend{};
+    size_t pend_m = 0;  // folded values (this rank's slice)
+    bool pending = false;
+    std::vector<FriRound> rounds;
+
+    // input: round 0's vector (this rank's n / comm.size elements of n);
+    // fold_area: as much again, for the folded vectors
+    FriCommit(lsp_ctx* ctx, Comm& comm, const Fr* input, Fr* fold_area, size_t n, std::vector<Fr>& roots,
+              AddOfLen add_of_len, size_t host_tree_top, size_t host_tail);
+    std::vector<Fr> commit(Challenger& ch);  // returns the final vector
+    // span: log the prover's "divide_by_height" line; rehearsal: no degree check
+    std::vector<Fr> final_poly(const std::vector<Fr>& fin, bool span, bool rehearsal) const;
+    // one query's commit-phase openings below the rank subtrees: per round the
+    // sibling's address and the path's; query_elems of them
+    void push_query(std::vector<uint64_t>& ptrs, size_t idx) const;
+    size_t query_elems() const;
+
+  private:
+    bool host_tail_fits() const;
+    void replicate();
+    void flush_fold();
+    void fri_device_round(Challenger& ch);
+    const Fr* fri_host_tail(Challenger& ch);
+    size_t fri_host_round(Challenger& ch, Fr* v, Fr* lay);
+};
+// the addresses of the path of `leaf` in a tree of `leaves` leaves laid out at `layers`
+void push_path(std::vector<uint64_t>& ptrs, const Fr* layers, size_t leaves, size_t leaf);
+// the elements at ptrs (device addresses), gathered by one kernel, on the host
+const Fr* gather_to_host(lsp_ctx* ctx, const std::vector<uint64_t>& ptrs);
+// the verifier.  fold_row: TwoAdicFriGenericConfig::fold_row.  fri_replay: the
+// roots into the transcript and the betas out of it, the final polynomial, the
+// proof-of-work witness; 0, 6 (a witness beyond 64 bits) or 7 (refused).
+// fri_check_query: one query's fold chain from `index` of the tallest vector
+// (2^lmax) against the roots -- ro_of_log_height(l): the reduced opening that
+// rolls in at height 2^l or nullptr; sib / path_len / path(k, l): round k's
+// opening, called in wire order -- and the final polynomial; 0, 10 or 11
+Fr fold_row(size_t index, uint32_t log_height, const Fr& beta, const Fr& e0, const Fr& e1);
+int fri_replay(Challenger& ch, const lsp_ctx* ctx, const std::vector<Fr>& roots, const std::vector<Fr>& final_poly,
+               const Fr& pow_w, std::vector<Fr>& betas);
+int fri_check_query(const P2Host& p2, const std::vector<Fr>& roots, const std::vector<Fr>& betas,
+                    const std::vector<Fr>& final_poly, uint32_t lmax, size_t index,
+                    const std::function<const Fr*(uint32_t)>& ro_of_log_height,
+                    const std::function<Fr(uint32_t)>& sib, const std::function<uint32_t(uint32_t)>& path_len,
+                    const std::function<Fr(uint32_t, uint32_t)>& path);
 // ---- pcs.cpp: TwoAdicFriPcs over batches of unequal heights
 // One opening problem as commit, open and verify all see it: per batch the LDE
 // heights and widths of its matrices in the caller's order, per matrix its points.

@@ -121,7 +121,7 @@ FoldSpec fold_spec(lsp_ctx* ctx, uint32_t logm, uint64_t i0, const Fr& beta) {
 }
 
 void fri_fold(lsp_ctx* ctx, const FoldSpec& f, size_t m) {
-    LSP_HIP(launch_fri_fold(f.v, m, f.half, f.half_beta, f.tab, f.L1, f.vout, ctx->stream, f.i0, (int)f.logm));
+    LSP_HIP(launch_fri_fold(f, m, ctx->stream));
 }
 
 // -------------------------------------------------------------- reduce

@@ -4,44 +4,11 @@
 #include <cstring>
 
 #include "prove_internal.hpp"
+#include "wire.hpp"
 
 namespace lsp {
 
 namespace {
-struct Reader {
-    const uint8_t* b;
-    size_t n, off = 0;
-    bool bad = false;
-    uint32_t u32() {
-        if (off + 4 > n) {
-            bad = true;
-            return 0;
-        }
-        uint32_t x = 0;
-        for (int i = 0; i < 4; ++i) x |= (uint32_t)b[off + i] << (8 * i);
-        off += 4;
-        return x;
-    }
-    Fr fr() {
-        Fr c = fr_zero();
-        if (off + 32 > n) {
-            bad = true;
-            return c;
-        }
-        for (int i = 0; i < 8; ++i) {
-            uint32_t x = 0;
-            for (int k = 0; k < 4; ++k) x |= (uint32_t)b[off + 4 * i + k] << (8 * k);
-            c.v[i] = x;
-        }
-        off += 32;
-        if (!fr_words_lt_mod(c)) {
-            bad = true;
-            return fr_zero();
-        }
-        return fr_from_canonical(c);
-    }
-};
-
 bool mk_verify(const P2Host& p2, const Fr& root, size_t index, const Fr* leaf, size_t nleaf, Reader& r,
                uint32_t expect) {
     const uint32_t pl = r.u32();
@@ -78,7 +45,7 @@ int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, 
     const size_t flen = (size_t)1 << ctx->log_final_poly_len;
     const Fr troot = r.fr(), qroot = r.fr();
     if (r.n - r.off < ((size_t)2 * w + q + 2 * (size_t)wp) * 32) return 5;  // (before any allocation by a claimed width)
-    std::vector<Fr> tl(w), tn(w), qc(q), pl(wp), pn(wp), roots(nr), betas(nr), fp(flen);
+    std::vector<Fr> tl(w), tn(w), qc(q), pl(wp), pn(wp), roots(nr), betas, fp(flen);
     for (auto& x : tl) x = r.fr();
     for (auto& x : tn) x = r.fr();
     for (auto& x : qc) x = r.fr();
@@ -109,16 +76,7 @@ int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, 
         for (const Fr& v : pn) ch.observe(v);
     }
     const Fr alpha_fri = ch.sample();
-    for (uint32_t k = 0; k < nr; ++k) {
-        ch.observe(roots[k]);
-        betas[k] = ch.sample();
-    }
-    if (TC.final_poly)
-        for (auto& c : fp) ch.observe(c);
-    const Fr pwc = fr_to_canonical(pw);
-    for (int i = 2; i < 8; ++i)
-        if (pwc.v[i]) return 6;
-    if (!ch.check_witness(ctx->pow_bits, (uint64_t)pwc.v[0] | ((uint64_t)pwc.v[1] << 32))) return 7;
+    if (const int bad = fri_replay(ch, ctx, roots, fp, pw, betas)) return bad;
     const Fr gN = host_two_adic_generator(logN);
     std::vector<Fr> trow(w), qrow(q), prow(wp);
     for (uint32_t qi = 0; qi < nq; ++qi) {
@@ -154,26 +112,12 @@ int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, 
             ro = fr_add(ro, fr_mul(apow, fr_mul(fr_sub(prow[c], pn[c]), dzn)));
             apow = fr_mul(apow, alpha_fri);
         }
-        Fr folded = ro;
-        size_t index = idx;
-        for (uint32_t k = 0; k < nr; ++k) {
-            const uint32_t log_folded = logN - 1 - k;
-            Fr ev[2];
-            ev[(index ^ 1) & 1] = r.fr();
-            ev[index & 1] = folded;
-            if (!mk_verify(ctx->p2, roots[k], index >> 1, ev, 2, r, log_folded)) return 10;
-            index >>= 1;
-            // TwoAdicFriGenericConfig::fold_row
-            const Fr s0 = fr_pow_u64(host_two_adic_generator(log_folded + 1), host_bitrev(index, log_folded));
-            const Fr s1 = fr_neg(s0);
-            folded = fr_add(ev[0], fr_mul(fr_mul(fr_sub(betas[k], s0), fr_sub(ev[1], ev[0])),
-                                          fr_inv(fr_sub(s1, s0))));
-        }
-        // final polynomial at x^(2^nr) (constant when log_final_poly_len = 0)
-        const Fr xf = fr_pow_u64(host_two_adic_generator(logN - nr), host_bitrev(index, logN - nr));
-        Fr ev = fr_zero();
-        for (size_t k = flen; k-- > 0;) ev = fr_add(fr_mul(ev, xf), fp[k]);
-        if (!fr_eq(ev, folded)) return 11;
+        // the commit-phase openings, read from the stream as the chain asks for them
+        const int bad = fri_check_query(
+            ctx->p2, roots, betas, fp, logN, idx, [&](uint32_t l) { return l == logN ? &ro : nullptr; },
+            [&](uint32_t) { return r.fr(); }, [&](uint32_t) { return r.u32(); },
+            [&](uint32_t, uint32_t) { return r.fr(); });
+        if (bad || r.bad) return bad ? bad : 10;
     }
     if (r.bad || r.off != r.n) return 12;
     // out-of-domain identity: folded_constraints(zeta) / Z_H(zeta) == sum zps_i * chunk_i

@@ -2,7 +2,7 @@
 (LSP_COOP_MAX, LSP_PAIR_MAX) are read once per process, so each setting proves
 in a process of its own and prints the proof's bytes in hex.
 
-    python tests/pcs_gpu_child.py case NAME    # a case of tests/pcs_cases.py
+    python tests/pcs_gpu_child.py case NAME... # cases of tests/pcs_cases.py, one WIRE line each
     python tests/pcs_gpu_child.py wide         # the ladder at true widths (test_gpu_pcs.wide_proof)
 """
 import os
@@ -22,11 +22,11 @@ from linea_stark_prover_amd.prover import Context  # noqa: E402
 def main():
     if sys.argv[1] == "wide":
         with Context(T.wide_config()) as ctx:
-            wire = T.wide_proof(ctx)[3]
-    else:
-        with Context(C.stark_config(sys.argv[2])) as ctx:
-            wire = T.gpu_open(ctx, sys.argv[2])[2]
-    print("WIRE " + wire.hex(), flush=True)
+            print("WIRE " + T.wide_proof(ctx)[3].hex(), flush=True)
+        return
+    for name in sys.argv[2:]:
+        with Context(C.stark_config(name)) as ctx:
+            print("WIRE " + T.gpu_open(ctx, name)[2].hex(), flush=True)
 
 
 if __name__ == "__main__":

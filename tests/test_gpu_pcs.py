@@ -2,9 +2,10 @@
 U15): lsp_pcs_commit / lsp_pcs_open against the big-integer reference of
 tests/pcs_ref.py on the shapes of tests/pcs_cases.py -- commitments, opened
 values and proofs byte for byte -- the existing prover's proof field by field
-on its own shape, and the lane forms of the fused fold-and-hash kernel (one
+on its own shape, the lane forms of the fused fold-and-hash kernel (one
 child process per setting; at true widths against the 4-lane form and the host
-verifier).  Everything is bit-exact.
+verifier), and the commit phase's host paths under roll-ins.  Everything is
+bit-exact.
 """
 import os
 import subprocess
@@ -174,12 +175,16 @@ def test_open_equals_the_provers_own_open(gpu_ctx):
 
 
 # ------------------------------------------------------------ lane forms
-def _child(args, env):
+def _child_wires(args, env, n):
     r = subprocess.run([sys.executable, os.path.join(HERE, "pcs_gpu_child.py")] + args, capture_output=True, text=True,
                        timeout=300, env=dict(os.environ, **env))
     wires = [x[5:] for x in r.stdout.splitlines() if x.startswith("WIRE ")]
-    assert r.returncode == 0 and len(wires) == 1, f"child ended with status {r.returncode}: {r.stderr[-2000:]}"
-    return bytes.fromhex(wires[0])
+    assert r.returncode == 0 and len(wires) == n, f"child ended with status {r.returncode}: {r.stderr[-2000:]}"
+    return [bytes.fromhex(w) for w in wires]
+
+
+def _child(args, env):
+    return _child_wires(args, env, 1)[0]
 
 
 @pytest.mark.parametrize("env", [{}, {"LSP_COOP_MAX": "16", "LSP_PAIR_MAX": "64"},
@@ -190,6 +195,24 @@ def test_roll_in_rounds_in_every_lane_form(product_lib, env):
     8 leaves, so with 16/64 they run with 1, 2 and 4 lanes per leaf, with 1/1
     all with 1, by default all with 4"""
     assert _child(["case", "ladder_2e10"], env) == C.reference("ladder_2e10").wire
+
+
+HOST_PATH_CASES = ["ladder", "gaps", "final_poly_len_1"]
+
+
+@pytest.mark.parametrize("env", [{"LSP_HOST_TREE_TOP": "8"}, {"LSP_HOST_TREE_TOP": "4", "LSP_FRI_HOST_TAIL": "16"}],
+                         ids=["top8", "top4_tail16"])
+def test_roll_in_rounds_on_the_host_paths(product_lib, env):
+    """The PCS runs the prover's commit phase with no host tree top and no host
+    tail; the environment gives it both.  Top 8: the last trees' leaves are hashed
+    on the host over a vector the plain fold kernel made with its roll-in (the
+    ladder rolls in at every length down to 16).  Top 4, tail 16: the host runs the
+    last rounds, and only from where no roll-in remains -- on the ladder the final
+    round alone, on gaps the rounds from length 32 (its roll-in) down.  The proofs
+    are the references' byte for byte."""
+    wires = _child_wires(["case"] + HOST_PATH_CASES, env, len(HOST_PATH_CASES))
+    for name, wire in zip(HOST_PATH_CASES, wires):
+        assert wire == C.reference(name).wire, name
 
 
 WIDE_LOGS = (14, 13, 12, 11, 10)  # LDE heights 2^17 ... 2^13: leaf batches of 64K ... 4K cross 32K and 16K

@@ -2,15 +2,22 @@
 // built and run under ASan + UBSan by tools/sanitize/run.sh (host code only;
 // no GPU is touched: a verifier-only context, LSP_HOST_ONLY).
 //
-//   driver <seed> <iterations> <proof.bin> <trace.cbor>...
+//   driver <seed> <iterations> <proof.bin> <trace.cbor | job>...
 //
 // For each input: the unmodified bytes, every truncation at a stride, and
 // <iterations> random mutations (byte flips, spliced length fields, appended
 // garbage) go through
 //   lsp_raw_trace_parse (+ lsp_raw_trace_shape / _columns)  -- cbor.cpp
 //   lsp_proof_deserialize (+ get_view / from_view / serialize round trip) and
-//   lsp_verify on a host-only context                        -- proof.cpp, verify.cpp
+//   lsp_verify on a host-only context                        -- proof.cpp, verify.cpp, fri.cpp, wire.hpp
 //   lsp_fr_from_be_bytes_mod_order on random lengths          -- host field code
+// A job file holds a proof with what its verifier is given besides (written by
+// tests/test_sanitize.py; words little-endian, elements as lsp_fr):
+//   "SANPCS01" u32 log_final_poly_len, pow_bits, num_queries, batches | per batch: commit, u32 matrices,
+//              per matrix u64 height, u64 width, u32 points, the points | u32 n, n observed elements | LSPPCS01 bytes
+//              -> lsp_pcs_verify after that transcript, lsp_pcs_proof_deserialize / _serialize   -- pcs.cpp, fri.cpp
+//   "SANPRP01" u32 air_len, the descriptor | u32 npub, public values | prep commit, u32 prep width | LSPPRF03 bytes
+//              -> lsp_verify_preprocessed, lsp_proof_deserialize                                  -- verify.cpp, proof.cpp
 // Any out-of-bounds access, leak-free UB or overflow aborts under the
 // sanitizers; logic failures (a parsed proof that does not re-serialize to
 // its input, an accepted corrupted proof) exit 1.
@@ -64,6 +71,135 @@ static std::vector<std::vector<uint8_t>> variants(const std::vector<uint8_t>& b,
         out.push_back(std::move(m));
     }
     return out;
+}
+
+// sequential reads of a job file's header (the job is the test's own, trusted)
+struct Job {
+    const std::vector<uint8_t>& b;
+    size_t off = 8;
+    template <class T>
+    T get() {
+        T x;
+        if (off + sizeof x > b.size()) {
+            std::fprintf(stderr, "short job file\n");
+            std::exit(2);
+        }
+        std::memcpy(&x, b.data() + off, sizeof x);
+        off += sizeof x;
+        return x;
+    }
+};
+
+static lsp_ctx* host_ctx(const std::vector<lsp_fr>& rc, uint32_t lfp, uint32_t pow_bits, uint32_t nq) {
+    lsp_params prm{};
+    prm.struct_size = sizeof prm;
+    prm.sbox_degree = 11;
+    prm.rounds_f = 8;
+    prm.rounds_p = 22;
+    prm.round_constants = rc.data();
+    prm.log_blowup = 3;
+    prm.log_final_poly_len = lfp;
+    prm.proof_of_work_bits = pow_bits;
+    prm.num_queries = nq;
+    prm.public_degree = 1;
+    lsp_ctx* ctx = nullptr;
+    if (lsp_ctx_create(LSP_HOST_ONLY, &prm, &ctx) != LSP_OK) std::exit(3);
+    return ctx;
+}
+
+// an LSPPCS01 proof with its verifier's arguments and transcript
+static int pcs_job(const std::vector<uint8_t>& file, const std::vector<lsp_fr>& rc, std::mt19937_64& rng, int iters,
+                   size_t& runs, size_t& parsed_ok) {
+    Job j{file};
+    const uint32_t lfp = j.get<uint32_t>(), pow_bits = j.get<uint32_t>(), nq = j.get<uint32_t>();
+    const uint32_t nb = j.get<uint32_t>();
+    std::vector<lsp_fr> commits, points, observed;
+    std::vector<size_t> nmats, heights, widths, npoints;
+    for (uint32_t b = 0; b < nb; ++b) {
+        commits.push_back(j.get<lsp_fr>());
+        nmats.push_back(j.get<uint32_t>());
+        for (size_t k = 0; k < nmats.back(); ++k) {
+            heights.push_back((size_t)j.get<uint64_t>());
+            widths.push_back((size_t)j.get<uint64_t>());
+            npoints.push_back(j.get<uint32_t>());
+            for (size_t i = 0; i < npoints.back(); ++i) points.push_back(j.get<lsp_fr>());
+        }
+    }
+    for (uint32_t n = j.get<uint32_t>(); n > 0; --n) observed.push_back(j.get<lsp_fr>());
+    const std::vector<uint8_t> wire(file.begin() + j.off, file.end());
+    lsp_ctx* ctx = host_ctx(rc, lfp, pow_bits, nq);
+    for (const auto& v : variants(wire, rng, iters)) {
+        ++runs;
+        lsp_challenger* ch = nullptr;
+        lsp_fr z;
+        if (lsp_challenger_create(ctx, &ch) != LSP_OK || lsp_challenger_observe(ch, observed.data(), observed.size()) != LSP_OK ||
+            lsp_challenger_sample(ch, &z) != LSP_OK)
+            return 3;
+        int check = 0;
+        const int rcv = lsp_pcs_verify(ctx, commits.data(), nb, nmats.data(), heights.data(), widths.data(), npoints.data(),
+                                       points.data(), v.data(), v.size(), ch, &check);
+        lsp_challenger_free(ch);
+        // (an empty vector's data() is null, which is a bad argument, not a proof)
+        if ((rcv == LSP_OK) != (v == wire) || (rcv != LSP_OK && rcv != LSP_E_VERIFY && !v.empty())) {
+            std::fprintf(stderr, "lsp_pcs_verify returned %d (check %d) on %s bytes\n", rcv, check,
+                         v == wire ? "the genuine" : "damaged");
+            return 1;
+        }
+        lsp_pcs_proof* p = nullptr;
+        const int rcd = lsp_pcs_proof_deserialize(v.data(), v.size(), &p);
+        if (rcd == LSP_OK) {
+            ++parsed_ok;
+            size_t n = 0;
+            lsp_pcs_proof_serialize(p, nullptr, 0, &n);
+            std::vector<uint8_t> back(n);
+            lsp_pcs_proof_serialize(p, back.data(), n, &n);
+            lsp_pcs_proof_free(p);
+            if (back != v) {
+                std::fprintf(stderr, "a parsed PCS proof serialized to other bytes (%zu)\n", v.size());
+                return 1;
+            }
+        } else if (rcd != LSP_E_ARG) {
+            std::fprintf(stderr, "lsp_pcs_proof_deserialize returned %d\n", rcd);
+            return 1;
+        }
+    }
+    lsp_ctx_destroy(ctx);
+    return 0;
+}
+
+// an LSPPRF03 proof with its AIR, public values and preprocessed commitment
+static int prep_job(const std::vector<uint8_t>& file, const std::vector<lsp_fr>& rc, std::mt19937_64& rng, int iters,
+                    size_t& runs, size_t& parsed_ok) {
+    Job j{file};
+    std::vector<int32_t> air(j.get<uint32_t>());
+    for (auto& x : air) x = j.get<int32_t>();
+    std::vector<lsp_fr> pub(j.get<uint32_t>());
+    for (auto& x : pub) x = j.get<lsp_fr>();
+    const lsp_fr commit = j.get<lsp_fr>();
+    const uint32_t wp = j.get<uint32_t>();
+    const std::vector<uint8_t> proof(file.begin() + j.off, file.end());
+    lsp_ctx* ctx = host_ctx(rc, 0, 0, 33);
+    for (const auto& v : variants(proof, rng, iters)) {
+        ++runs;
+        const int rcv = lsp_verify_preprocessed(ctx, air.data(), air.size(), pub.data(), pub.size(), &commit, wp, v.data(),
+                                                v.size());
+        if ((rcv == LSP_OK) != (v == proof) || (rcv != LSP_OK && rcv != LSP_E_VERIFY && !v.empty())) {
+            std::fprintf(stderr, "lsp_verify_preprocessed returned %d on %s bytes: %s\n", rcv,
+                         v == proof ? "the genuine" : "damaged", lsp_last_error(nullptr));
+            return 1;
+        }
+        lsp_proof* p = nullptr;
+        const int rcd = lsp_proof_deserialize(v.data(), v.size(), &p);
+        if (rcd == LSP_OK) {
+            ++parsed_ok;
+            lsp_proof_free(p);
+        } else if (rcd != LSP_E_ARG) {
+            std::fprintf(stderr, "lsp_proof_deserialize returned %d\n", rcd);
+            return 1;
+        }
+    }
+    lsp_ctx_destroy(ctx);
+    return 0;
 }
 
 int main(int argc, char** argv) {
@@ -135,9 +271,15 @@ int main(int argc, char** argv) {
         }
     }
 
-    // ---- CBOR traces
+    // ---- job files and CBOR traces
     for (int a = 4; a < argc; ++a) {
         const std::vector<uint8_t> t = slurp(argv[a]);
+        if (t.size() >= 8 && (!std::memcmp(t.data(), "SANPCS01", 8) || !std::memcmp(t.data(), "SANPRP01", 8))) {
+            const int r = t[3] == 'P' && t[4] == 'C' ? pcs_job(t, rc, rng, iters, runs, parsed_ok)
+                                                     : prep_job(t, rc, rng, iters, runs, parsed_ok);
+            if (r) return r;
+            continue;
+        }
         for (const auto& v : variants(t, rng, iters)) {
             ++runs;
             lsp_raw_trace* rt = nullptr;

@@ -3,7 +3,10 @@
 # code is unchanged: each -fsanitize= sits behind -Xarch_host) and of the fuzz
 # driver (driver.cpp), then a run over a proof and the CBOR fixtures.
 #
-#   tools/sanitize/run.sh <proof.bin> [iterations] [seed]
+#   tools/sanitize/run.sh <proof.bin> [iterations] [seed] [job file...]
+#
+# job files: a PCS proof or a proof with a preprocessed matrix, each with its
+# verifier's arguments (driver.cpp; tests/test_sanitize.py writes them)
 #
 # Objects and binaries go to tools/sanitize/_build (git-ignored); sources are
 # rebuilt only when newer than their object.  CPU only: no GPU is used.
@@ -39,4 +42,4 @@ $CLANG -O1 -g -std=c++17 -fsanitize=address,undefined -shared-libsan -fno-omit-f
   "$HERE/driver.cpp" -o "$OUT/driver" -L "$OUT" -llsp_hip_asan -Wl,-rpath,"$OUT" -Wl,-rpath,"$RTDIR"
 # leak checking is off: the HIP runtime's own one-time allocations are not ours
 ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
-  "$OUT/driver" "${3:-1}" "${2:-300}" "$1" "$ROOT/tests/golden/perm_small.cbor" "$ROOT/tests/golden/lookup_small.cbor"
+  "$OUT/driver" "${3:-1}" "${2:-300}" "$1" "$ROOT/tests/golden/perm_small.cbor" "$ROOT/tests/golden/lookup_small.cbor" "${@:4}"
