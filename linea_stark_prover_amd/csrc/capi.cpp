@@ -941,21 +941,9 @@ int lsp_open_reduce(lsp_ctx* ctx, const lsp_fr* mat, size_t n, size_t w, const l
         const Fr* dm = dev_in(ctx, mat, n * w, mem, "api_in");
         const Fr* dinv = dev_in(ctx, inv_denoms, npoints * n, mem, "api_in2");
         Fr* dro = const_cast<Fr*>(dev_in(ctx, ro, n, mem, "api_out"));
-        // host side: alpha^c (c < w), then per point the offset, then per point offset * sum_c alpha^c y_c
-        std::vector<Fr> coef = alpha_powers(to_fr(*alpha), w + 1);
-        const Fr aw = coef[w];  // alpha^w: the offset advances by the matrix width
-        coef.resize(w + 2 * npoints);
         const std::vector<Fr> y = to_frs(ys, npoints * w);
         Fr off = to_fr(*alpha_pow_offset);
-        for (size_t p = 0; p < npoints; ++p) {
-            coef[w + p] = off;
-            coef[w + npoints + p] = fr_mul(off, reduce_opened(coef.data(), y.data() + p * w, w));
-            off = fr_mul(off, aw);
-        }
-        Fr* dc = ctx->fbuf("api_coef", w + 2 * npoints);
-        ctx->h2d_async("api_coef_h", dc, coef.data(), coef.size() * sizeof(Fr));
-        LSP_HIP(launch_reduce_matrix(dm, n, (uint32_t)w, dc, (uint32_t)npoints, dinv, dc + w, dc + w + npoints, dro,
-                                     ctx->stream));
+        reduce_matrix(ctx, dm, n, w, dinv, y.data(), npoints, to_fr(*alpha), off, dro, "api_coef");
         finish_out(ctx, ro, dro, n, mem);
         *alpha_pow_offset = from_fr(off);
     });

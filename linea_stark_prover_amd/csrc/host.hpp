@@ -341,22 +341,39 @@ void Air::eval(const Fr* loc, const Fr* nxt, const Fr* pub, const Fr& first, con
         });
 }
 
+// A proof's committed matrices: trace (opened at zeta, zeta w_h), quotient
+// chunks (zeta), then the preprocessed matrix when present (zeta, zeta w_h) --
+// the order of the wire, the transcript and the running power of alpha_fri
+enum : size_t { MAT_TRACE = 0, MAT_QUOTIENT = 1, MAT_PREP = 2 };
+// One of them.  The preprocessed matrix's root is the verifier's own input, so
+// it is not on the wire.
+struct OpenedMat {
+    uint32_t width, npoints;
+    bool root_on_wire;
+    Fr root = fr_zero();
+    std::vector<Fr> ys;  // [point][column]
+    OpenedMat(size_t m, uint32_t w) : width(w), npoints(m == MAT_QUOTIENT ? 1 : 2), root_on_wire(m != MAT_PREP) {}
+    const Fr* at(uint32_t point) const { return ys.data() + (size_t)point * width; }
+};
+
 struct lsp_query {
-    std::vector<Fr> trow, tpath, qrow, qpath, sib;
+    struct Opening {
+        std::vector<Fr> row, path;
+    };
+    std::vector<Opening> open;  // one per committed matrix, in the proof's order
+    std::vector<Fr> sib;
     std::vector<std::vector<Fr>> fpath;
-    std::vector<Fr> prow, ppath;  // the preprocessed matrix's opening (LSPPRF03 only)
 };
 
 }  // namespace lsp
 
 struct lsp_proof {
-    uint32_t log_h = 0, log_q = 0, w = 0;
-    lsp::Fr troot, qroot, pow_w;
-    std::vector<lsp::Fr> tl, tn, qc, roots, final_poly;
-    // a proof over an AIR with a preprocessed matrix (wire format "LSPPRF03"):
-    // its width (0: none, "LSPPRF02") and its opened values at zeta and zeta w
-    uint32_t wp = 0;
-    std::vector<lsp::Fr> pl, pn;
+    uint32_t log_h = 0, log_q = 0;
+    // the committed matrices (lsp::MAT_*): two is wire format "LSPPRF02", a
+    // third -- the preprocessed matrix -- "LSPPRF03"
+    std::vector<lsp::OpenedMat> mats;
+    lsp::Fr pow_w;
+    std::vector<lsp::Fr> roots, final_poly;
     std::vector<lsp::lsp_query> queries;
     // made under a rehearsal transport (lsp_ctx_attach_loopback): peers' data
     // fabricated, so not a proof -- serialize / view refuse it (shape queries only)
@@ -365,8 +382,7 @@ struct lsp_proof {
     // be shared across threads, e.g. rayon tasks): built under cache_mu
     mutable std::mutex cache_mu;
     mutable std::vector<uint8_t> wire;  // serialize() result, cached by lsp_proof_serialize
-    mutable std::shared_ptr<void> view_cache;  // flat arrays behind lsp_proof_view (proof.cpp)
-    mutable std::shared_ptr<void> prep_view_cache;  // ... behind lsp_proof_preprocessed_view
+    mutable std::shared_ptr<void> view_cache;  // flat arrays behind both views (proof.cpp)
 };
 
 // a parsed CBOR RawPermutationTrace / RawLookupTrace (cbor.cpp)

@@ -194,69 +194,97 @@ __global__ __launch_bounds__(256) void k_reduce_rows(ReduceArgs a) {
     a.out[i] = fr_reduce_once(f29_repack_out(f29_reduce_qt(f29_lazy3(t1, t2, t3), qt)));  // < 24.3 r in
 }
 
-// The preprocessed matrix's two terms of the FRI input, added to what
-// k_reduce_rows wrote (PrepReduceArgs, kernels.hpp).  As there: the alpha
-// powers once per workgroup into LDS in the 29-bit form, the row's elements
-// (ark form) times them on the 29-bit product, at most RR_CHUNK products per
-// lazy sum, the next chunk of the row requested before the current chunk's
-// products.  Bounds: rr < 2 r; ry - rr through f29_sub16 < 17 r; times an
-// inverse denominator (< 2 r) < 8.1 r; times the offset (< 2 r) < 8.1 r; two
-// such terms and the old value (canonical) < 17.2 r into f29_reduce_qt.
-__global__ __launch_bounds__(256) void k_reduce_prep(PrepReduceArgs a) {
-    extern __shared__ uint4 rp_lds[];
-    uint4* qt = rp_lds;  // 3 * F29_QTAB_N
-    F29* apw29 = reinterpret_cast<F29*>(rp_lds + 3 * F29_QTAB_N);
+// One matrix's terms of a reduced opening at npts points, added to ro (the
+// prover's matrices after the fused pair, the PCS, lsp_open_reduce):
+//   ro[i] += sum_p (offys[p] - off[p] rr_i) inv[p n + i],  rr_i = sum_c apw[c] M[i][c]
+// As k_reduce_rows: the alpha powers once per workgroup into LDS in the 29-bit
+// form (GLB: from consts29, k_matrix_consts), RR_CHUNK products per lazy sum, the
+// row's next chunk requested before the current one's products, and the first
+// MR_POINTS inverse denominators before the row.  off / offys: wave-uniform loads.
+// Bounds, for any 256-bit words in M, inv, off, offys and ro (lsp_open_reduce
+// passes a caller's on; 2^256 < 13.71 r, r / 2^261 < 0.0023): a word times a
+// 29-bit-form constant (f29_from_fr: < 2 r) is < 8.07 r, so RR_CHUNK products
+// and rr (< 2 r) are < 26.3 r with limbs < 2^31 into f29_reduce_qt, rr < 2 r
+// out.  Per point: rr off < 8.01 r, normalised (f29_sub16's subtrahend bound is
+// 16 r); offys + 16 r - rr off < 29.72 r with limbs < 1.5 2^30; times the
+// inverse denominator (< 2 r, normalised) < 8.14 r, normalised.  The sum starts
+// as the old ro (< 13.71 r, normalised) and takes MR_POINTS terms between
+// reductions: < 13.71 r + 2 * 8.14 r < 30 r < 64 r from three normalised
+// operands, limbs < 1.5 2^30 -- whatever npts is.  The result is canonical.
+constexpr uint32_t MR_POINTS = 2;
+struct MatrixReduceArgs {
+    const Fr *M, *apw, *inv, *off, *offys;  // M: n x w
+    Fr* ro;
+    F29* consts29;
+    size_t n, lds_max;
+    uint32_t w, npts;
+};
+
+__global__ __launch_bounds__(256) void k_matrix_consts(MatrixReduceArgs a) {
+    const size_t k = gtid();
+    if (k < a.w) a.consts29[k] = f29_from_fr(a.apw[k]);
+}
+
+template <bool GLB>
+__global__ __launch_bounds__(256) void k_reduce_matrix(MatrixReduceArgs a) {
+    extern __shared__ uint4 rm_lds[];
+    uint4* qt = rm_lds;  // 3 * F29_QTAB_N
+    const F29* apw29 = a.consts29;
     f29_qtab_init(qt);
-    // the alpha powers' LDS copy: the launch sized it for wp entries after the table
+    // the alpha powers' LDS copy: the launch sized it for w entries after the table
     // (wave-uniform, so every lane reaches the barrier or none does)
-    const bool fits = LSP_BOUNDS(3 * F29_QTAB_N * sizeof(uint4) + (size_t)a.wp * sizeof(F29) <= a.lds_max);
-    if (fits)
-        for (uint32_t k = threadIdx.x; k < a.wp; k += blockDim.x) apw29[k] = f29_from_fr(a.apw[k]);
+    const bool fits = LSP_BOUNDS(GLB || 3 * F29_QTAB_N * sizeof(uint4) + (size_t)a.w * sizeof(F29) <= a.lds_max);
+    if constexpr (!GLB) {
+        F29* c = reinterpret_cast<F29*>(rm_lds + 3 * F29_QTAB_N);
+        if (fits)
+            for (uint32_t k = threadIdx.x; k < a.w; k += blockDim.x) c[k] = f29_from_fr(a.apw[k]);
+        apw29 = c;
+    }
     __syncthreads();
     const size_t i = gtid();
     if (i >= a.n || !fits) return;
-    const Fr* row = a.prep + i * a.wp;
-    constexpr uint32_t RC = RR_CHUNK;
+    const Fr* row = a.M + i * a.w;
+    constexpr uint32_t RC = RR_CHUNK, PC = MR_POINTS;
     auto load = [&](uint32_t k, Fr* dst) {
 #pragma unroll
         for (uint32_t j = 0; j < RC; ++j)
-            if (k + j < a.wp) dst[j] = row[k + j];
+            if (k + j < a.w) dst[j] = row[k + j];
     };
-    const Fr zi = a.inv_z[i], zni = a.inv_zn[i], old = a.out[i];
-    Fr cur[RC], nxt[RC];
+    Fr iv[PC], cur[RC], nxt[RC];
+    auto load_inv = [&](uint32_t p) {
+#pragma unroll
+        for (uint32_t j = 0; j < PC; ++j)
+            if (p + j < a.npts) iv[j] = a.inv[(size_t)(p + j) * a.n + i];
+    };
+    load_inv(0);
+    const Fr old = a.ro[i];
     load(0, cur);
     F29 rr = f29_zero();
-    for (uint32_t k = 0; k < a.wp; k += RC) {
-        if (k + RC < a.wp) load(k + RC, nxt);
+    for (uint32_t k = 0; k < a.w; k += RC) {
+        if (k + RC < a.w) load(k + RC, nxt);
         F29 s = rr;
 #pragma unroll
         for (uint32_t j = 0; j < RC; ++j)
-            if (k + j < a.wp) s = f29_lazy2(s, f29_mul(f29_repack_in(cur[j]), apw29[k + j]));  // < 8.06 r each
+            if (k + j < a.w) s = f29_lazy2(s, f29_mul(f29_repack_in(cur[j]), apw29[k + j]));  // < 8.07 r each
         rr = f29_reduce_qt(s, qt);  // < 2 r
-        if (k + RC < a.wp) {
+        if (k + RC < a.w) {
 #pragma unroll
             for (uint32_t j = 0; j < RC; ++j) cur[j] = nxt[j];
         }
     }
-    const F29 t1 = f29_mul(f29_mul(f29_sub16(f29_repack_in(a.ry_z), rr), f29_from_fr(zi)), f29_from_fr(a.off_z));
-    const F29 t2 = f29_mul(f29_mul(f29_sub16(f29_repack_in(a.ry_zn), rr), f29_from_fr(zni)), f29_from_fr(a.off_zn));
-    a.out[i] = fr_reduce_once(f29_repack_out(f29_reduce_qt(f29_lazy3(t1, t2, f29_repack_in(old)), qt)));
-}
-
-// coef[0..npts) = alpha offsets, coef[npts..2 npts) = offset * reduced ys; apw = alpha^c, c < w
-__global__ __launch_bounds__(256) void k_reduce_matrix(const Fr* __restrict__ M, size_t n, uint32_t w,
-                                                       const Fr* __restrict__ apw, uint32_t npts,
-                                                       const Fr* __restrict__ inv, const Fr* __restrict__ off,
-                                                       const Fr* __restrict__ offys, Fr* __restrict__ ro) {
-    const size_t i = gtid();
-    if (i >= n) return;
-    const Fr* row = M + i * w;
-    Fr rr = fr_zero();
-    for (uint32_t c = 0; c < w; ++c) rr = fr_add(rr, fr_mul(apw[c], row[c]));
-    Fr acc = ro[i];
-    for (uint32_t p = 0; p < npts; ++p)
-        acc = fr_add(acc, fr_mul(fr_sub(offys[p], fr_mul(off[p], rr)), inv[(size_t)p * n + i]));
-    ro[i] = acc;
+    F29 acc = f29_repack_in(old);
+    for (uint32_t p = 0; p < a.npts; p += PC) {
+        if (p) load_inv(p);  // (only the first MR_POINTS are requested ahead of the row)
+        F29 s = acc;
+#pragma unroll
+        for (uint32_t j = 0; j < PC; ++j)
+            if (p + j < a.npts) {
+                const F29 d = f29_sub16(f29_repack_in(a.offys[p + j]), f29_mul(rr, f29_from_fr(a.off[p + j])));
+                s = f29_lazy2(s, f29_mul(d, f29_from_fr(iv[j])));  // < 8.14 r each
+            }
+        acc = f29_reduce_qt(s, qt);  // < 2 r
+    }
+    a.ro[i] = fr_reduce_once(f29_repack_out(acc));
 }
 }  // namespace
 
@@ -300,22 +328,17 @@ hipError_t launch_reduce_rows(const ReduceArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-bool reduce_prep_fits(uint32_t wp, size_t lds_max) {
-    return 3 * F29_QTAB_N * sizeof(uint4) + (size_t)wp * sizeof(F29) <= lds_max;
-}
-
-hipError_t launch_reduce_prep(const PrepReduceArgs& a, hipStream_t st) {
-    if (!a.prep || !a.wp || !a.inv_z || !a.inv_zn || !a.apw || !a.out || !reduce_prep_fits(a.wp, a.lds_max))
-        return hipErrorInvalidValue;
-    const size_t lds = 3 * F29_QTAB_N * sizeof(uint4) + (size_t)a.wp * sizeof(F29);
-    return launch_lds(k_reduce_prep, nblocks(a.n, 256), 256, lds, st, a);
-}
-
 hipError_t launch_reduce_matrix(const Fr* M, size_t n, uint32_t w, const Fr* apw, uint32_t npts, const Fr* inv,
-                                const Fr* off, const Fr* offys, Fr* ro, hipStream_t st) {
-    hipLaunchKernelGGL(k_reduce_matrix, dim3(nblocks(n, 256)), dim3(256), 0, st, M, n, w, apw, npts, inv, off, offys,
-                       ro);
-    return hipGetLastError();
+                                const Fr* off, const Fr* offys, Fr* ro, size_t lds_max, F29* consts29,
+                                hipStream_t st) {
+    if (!M || !n || !w || !npts || !apw || !inv || !off || !offys || !ro) return hipErrorInvalidValue;
+    const MatrixReduceArgs a{M, apw, inv, off, offys, ro, consts29, n, lds_max, w, npts};
+    const size_t qtab = 3 * F29_QTAB_N * sizeof(uint4);
+    if (!reduce_matrix_scratch(w, lds_max))
+        return launch_lds(k_reduce_matrix<false>, nblocks(n, 256), 256, qtab + (size_t)w * sizeof(F29), st, a);
+    if (!consts29) return hipErrorInvalidValue;  // the caller must pass the global scratch (reduce_matrix_scratch)
+    hipLaunchKernelGGL(k_matrix_consts, dim3(nblocks(w, 256)), dim3(256), 0, st, a);
+    return launch_lds(k_reduce_matrix<true>, nblocks(n, 256), 256, qtab, st, a);
 }
 
 }  // namespace lsp

@@ -335,27 +335,6 @@ inline size_t reduce_rows_scratch(uint32_t w, uint32_t q, size_t lds_max) {
     return lds <= lds_max ? 0 : w + 1 + 2 * (size_t)q;
 }
 hipError_t launch_reduce_rows(const ReduceArgs& a, hipStream_t st);
-// The preprocessed matrix as a third matrix at two points, accumulated into the
-// FRI input launch_reduce_rows wrote (proofs with a preprocessed matrix only):
-//   out[i] += off_z (ry_z - rr_i) inv_z[i] + off_zn (ry_zn - rr_i) inv_zn[i],
-//   rr_i = sum_c apw[c] prep[i][c], c < wp
-// with off_z = alpha_fri^(2w+q), off_zn = alpha_fri^(2w+q+wp) continuing the
-// running power and ry_* the opened values reduced by apw.  One pass over the
-// N x wp matrix on the 29-bit product, the alpha powers in the workgroup's LDS.
-struct PrepReduceArgs {
-    const Fr* prep;  // N x wp
-    uint32_t wp;
-    const Fr* inv_z;
-    const Fr* inv_zn;
-    const Fr* apw;  // alpha_fri^c, c < wp (device)
-    Fr ry_z, ry_zn, off_z, off_zn;
-    Fr* out;  // N, read and written
-    size_t n;
-    size_t lds_max = 64 * 1024;
-};
-// whether wp alpha powers fit the workgroup's LDS beside the reduction table (about 4,400 columns on gfx950)
-bool reduce_prep_fits(uint32_t wp, size_t lds_max);
-hipError_t launch_reduce_prep(const PrepReduceArgs& a, hipStream_t st);
 // one deliberately failing LSP_BOUNDS check (dbg_bounds.hpp; a no-op kernel in the product build)
 hipError_t launch_bounds_probe(uint32_t* sink, hipStream_t st);
 #ifdef LSP_DEBUG_BOUNDS
@@ -370,9 +349,16 @@ unsigned bounds_fault_k_check();
 unsigned bounds_fault_k_merkle_inject();
 unsigned bounds_fault_k_fri();
 #endif
-// one matrix opened at npts points (the generic reduce of TwoAdicFriPcs::open):
+// one matrix opened at npts >= 1 points (the generic reduce of TwoAdicFriPcs::open;
+// the prover's matrices after the pair launch_reduce_rows fuses), all device memory:
 // ro[i] += sum_p (offys[p] - off[p] * sum_c apw[c] M[i][c]) * inv[p*n + i]
+// The w alpha powers stay in the workgroup's LDS beside the 3 KiB reduction table
+// up to lds_max; wider matrices keep them in global memory (consts29: w F29)
+inline size_t reduce_matrix_scratch(uint32_t w, size_t lds_max) {
+    return 3 * 64 * 16 + (size_t)w * 36 <= lds_max ? 0 : w;
+}
 hipError_t launch_reduce_matrix(const Fr* M, size_t n, uint32_t w, const Fr* apw, uint32_t npts, const Fr* inv,
-                                const Fr* off, const Fr* offys, Fr* ro, hipStream_t st);
+                                const Fr* off, const Fr* offys, Fr* ro, size_t lds_max, F29* consts29,
+                                hipStream_t st);
 
 }  // namespace lsp

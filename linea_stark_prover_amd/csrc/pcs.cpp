@@ -197,10 +197,13 @@ std::unique_ptr<lsp_pcs_proof> pcs_open(lsp_ctx* ctx, const lsp_tree* const* tre
             }
         Fr* dc = ctx->fbuf("pcs_coef", coef.size());
         ctx->h2d_async("pcs_coef_h", dc, coef.data(), coef.size() * sizeof(Fr));
+        F29* consts29 = nullptr;  // alpha powers beyond the LDS: global (every launch's are a prefix of the widest's)
+        if (const size_t nsc = reduce_matrix_scratch((uint32_t)maxw, ctx->lds_per_block))
+            consts29 = (F29*)ctx->buf("pcs_coef_29", nsc * sizeof(F29));
         for (size_t j = 0; j < todo.size(); ++j) {
             const Launch& l = todo[j];
             LSP_HIP(launch_reduce_matrix(l.M, l.N, (uint32_t)l.w, dc, 1, l.inv, dc + maxw + 2 * j, dc + maxw + 2 * j + 1,
-                                         l.ro, st));
+                                         l.ro, ctx->lds_per_block, consts29, st));
         }
     }
     // ---- FRI commit phase (fri.cpp): each shorter vector rolls in where the
@@ -384,27 +387,6 @@ int pcs_verify_host(const lsp_ctx* ctx, const Fr* commits, PcsRounds& R, const u
     std::vector<Fr> betas;
     if (const int bad = fri_replay(ch, ctx, p.roots, p.final_poly, p.pow_w, betas)) return bad;
 
-    // per (matrix, point): the running power of its height and the reduced opened values times it
-    size_t maxw = 0;
-    for (const auto& B : R.batches)
-        for (const auto& m : B) maxw = std::max(maxw, m.width);
-    const std::vector<Fr> apw = alpha_powers(alpha, maxw + 1);
-    std::vector<Fr> offs, offys;
-    {
-        std::map<uint32_t, Fr> off;
-        size_t o = 0;
-        for (const auto& B : R.batches)
-            for (const auto& m : B) {
-                const uint32_t logN = log2_exact(m.N);
-                for (size_t k = 0; k < m.points.size(); ++k) {
-                    Fr& f = off.emplace(logN, one).first->second;
-                    offs.push_back(f);
-                    offys.push_back(fr_mul(f, reduce_opened(apw.data(), p.ys.data() + o, m.width)));
-                    f = fr_mul(f, apw[m.width]);
-                    o += m.width;
-                }
-            }
-    }
     struct Batch {
         std::vector<HeightClass> cls;
         std::vector<size_t> widths;
@@ -422,8 +404,10 @@ int pcs_verify_host(const lsp_ctx* ctx, const Fr* commits, PcsRounds& R, const u
     }
     for (const lsp_pcs_proof::Query& q : p.queries) {
         const size_t idx = (size_t)ch.sample_bits(lmax);
-        std::map<uint32_t, Fr> ro;  // by log2 of the LDE height
-        size_t kp = 0;
+        // by log2 of the LDE height: the reduced opening, and the running power
+        // of alpha, which runs across the batches in order
+        std::map<uint32_t, Fr> ro, apow;
+        const Fr* ys = p.ys.data();
         for (size_t k = 0; k < nb; ++k) {
             const Batch& B = batches[k];
             const size_t ib = idx >> (lmax - B.logN);
@@ -439,12 +423,10 @@ int pcs_verify_host(const lsp_ctx* ctx, const Fr* commits, PcsRounds& R, const u
                 if (!m.points.empty()) {
                     const Fr x = fr_mul(GEN, fr_pow_u64(host_two_adic_generator(logN),
                                                         host_bitrev(idx >> (lmax - logN), logN)));
-                    const Fr rr = reduce_opened(apw.data(), row, m.width);
                     Fr& acc = ro.emplace(logN, fr_zero()).first->second;
-                    for (const Fr& z : m.points) {
-                        acc = fr_add(acc, fr_mul(fr_sub(offys[kp], fr_mul(offs[kp], rr)), fr_inv(fr_sub(z, x))));
-                        ++kp;
-                    }
+                    acc = fr_add(acc, reduced_opening_term(row, ys, m.width, m.points.data(), m.points.size(), x, alpha,
+                                                           apow.emplace(logN, one).first->second));
+                    ys += m.width * m.points.size();
                 }
                 row += m.width;
             }

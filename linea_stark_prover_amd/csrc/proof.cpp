@@ -76,26 +76,20 @@ std::vector<lsp_query> recycled_queries() {
     return v;
 }
 
+// two committed matrices: "LSPPRF02"; a third, the preprocessed one: "LSPPRF03" 
 std::vector<uint8_t> serialize(const lsp_proof& p, HostPool* pool, std::vector<uint8_t>* reuse) {
-    // with a preprocessed matrix (p.wp > 0) the format is LSPPRF03: prep_width after
-    // final_poly_len, the two opened rows after the chunks', a third opening per query
-    const bool prep = p.wp != 0;
-    size_t nfr = 3 + p.tl.size() + p.tn.size() + p.qc.size() + p.roots.size() + p.final_poly.size(), nu32 = 6;
-    if (prep) {
-        nfr += p.pl.size() + p.pn.size();
-        nu32 += 1;
-    }
+    const size_t nm = p.mats.size();
+    LSP_REQUIRE(nm == 2 || nm == 3, LSP_E_STATE, "a proof holds two or three committed matrices");
+    size_t nfr = 1 + p.roots.size() + p.final_poly.size(), nu32 = 4 + nm;
+    for (const OpenedMat& m : p.mats) nfr += m.ys.size() + (m.root_on_wire ? 1 : 0);
     // byte offset of every query's record (queries are written independently)
     std::vector<size_t> qoff(p.queries.size() + 1);
     size_t qbytes = 0;
     for (size_t i = 0; i < p.queries.size(); ++i) {
         const auto& q = p.queries[i];
-        size_t f = q.trow.size() + q.tpath.size() + q.qrow.size() + q.qpath.size() + q.sib.size(), u = 2 + q.sib.size();
+        size_t f = q.sib.size(), u = q.open.size() + q.sib.size();
+        for (auto& o : q.open) f += o.row.size() + o.path.size();
         for (auto& fp : q.fpath) f += fp.size();
-        if (prep) {
-            f += q.prow.size() + q.ppath.size();
-            u += 1;
-        }
         qoff[i] = qbytes;
         qbytes += 32 * f + 4 * u;
     }
@@ -105,24 +99,18 @@ std::vector<uint8_t> serialize(const lsp_proof& p, HostPool* pool, std::vector<u
     // every byte is written below, so a recycled buffer needs no clearing
     // (resize value-initialises only what it adds)
     b.resize(head + qbytes);
-    std::memcpy(b.data(), prep ? "LSPPRF03" : "LSPPRF02", 8);
+    std::memcpy(b.data(), nm == 3 ? "LSPPRF03" : "LSPPRF02", 8);
     Writer w{b.data() + 8};
     w.u32(p.log_h);
     w.u32(p.log_q);
-    w.u32(p.w);
+    w.u32(p.mats[MAT_TRACE].width);
     w.u32((uint32_t)p.queries.size());
     w.u32((uint32_t)p.roots.size());
     w.u32((uint32_t)p.final_poly.size());
-    if (prep) w.u32(p.wp);
-    w.fr(p.troot);
-    w.fr(p.qroot);
-    w.frs(p.tl);
-    w.frs(p.tn);
-    w.frs(p.qc);
-    if (prep) {
-        w.frs(p.pl);
-        w.frs(p.pn);
-    }
+    for (size_t m = MAT_QUOTIENT + 1; m < nm; ++m) w.u32(p.mats[m].width);
+    for (const OpenedMat& m : p.mats)
+        if (m.root_on_wire) w.fr(m.root);
+    for (const OpenedMat& m : p.mats) w.frs(m.ys);
     w.frs(p.roots);
     w.frs(p.final_poly);
     w.fr(p.pow_w);
@@ -130,21 +118,13 @@ std::vector<uint8_t> serialize(const lsp_proof& p, HostPool* pool, std::vector<u
     auto write_query = [&](size_t i) {
         const auto& q = p.queries[i];
         Writer wq{b.data() + head + qoff[i]};
-        wq.frs(q.trow);
-        wq.u32((uint32_t)q.tpath.size());
-        wq.frs(q.tpath);
-        wq.frs(q.qrow);
-        wq.u32((uint32_t)q.qpath.size());
-        wq.frs(q.qpath);
-        if (prep) {
-            wq.frs(q.prow);
-            wq.u32((uint32_t)q.ppath.size());
-            wq.frs(q.ppath);
+        for (auto& o : q.open) {
+            wq.frs(o.row);
+            wq.path(o.path);
         }
         for (size_t r = 0; r < q.sib.size(); ++r) {
             wq.fr(q.sib[r]);
-            wq.u32((uint32_t)q.fpath[r].size());
-            wq.frs(q.fpath[r]);
+            wq.path(q.fpath[r]);
         }
     };
     if (pool && p.queries.size() > 1)
@@ -165,38 +145,33 @@ lsp_proof* deserialize(const uint8_t* buf, size_t len) {
     auto p = std::make_unique<lsp_proof>();
     p->log_h = r.u32();
     p->log_q = r.u32();
-    p->w = r.u32();
-    const uint32_t nq = r.u32(), nr = r.u32(), nf = r.u32();
+    const uint32_t w = r.u32(), nq = r.u32(), nr = r.u32(), nf = r.u32();
     // LSPPRF03: the preprocessed matrix's width, range-checked like the trace's
     // before anything is sized by it (Reader::frs refuses what the bytes cannot hold)
-    p->wp = prep ? r.u32() : 0;
-    if (prep && (r.bad || p->wp == 0 || p->wp > (1u << 20))) throw LspError(LSP_E_ARG, "proof header out of range");
-    if (r.bad || p->log_h > 40 || p->log_q > 20 || p->w == 0 || p->w > (1u << 20) || nr > 64 || nq > (1u << 20) ||
+    const uint32_t wp = prep ? r.u32() : 0;
+    if (prep && (r.bad || wp == 0 || wp > (1u << 20))) throw LspError(LSP_E_ARG, "proof header out of range");
+    if (r.bad || p->log_h > 40 || p->log_q > 20 || w == 0 || w > (1u << 20) || nr > 64 || nq > (1u << 20) ||
         nf == 0 || nf > (1u << 20) || (nf & (nf - 1)) != 0)
         throw LspError(LSP_E_ARG, "proof header out of range");
-    const size_t q = (size_t)1 << p->log_q;
-    p->troot = r.fr();
-    p->qroot = r.fr();
-    r.frs(p->tl, p->w);
-    r.frs(p->tn, p->w);
-    r.frs(p->qc, q);
-    if (prep) {
-        r.frs(p->pl, p->wp);
-        r.frs(p->pn, p->wp);
+    const uint32_t widths[] = {w, 1u << p->log_q, wp};
+    size_t wsum = 0;
+    for (size_t m = 0; m < (prep ? 3u : 2u); ++m) {
+        p->mats.emplace_back(m, widths[m]);
+        wsum += widths[m];
     }
+    for (OpenedMat& m : p->mats)
+        if (m.root_on_wire) m.root = r.fr();
+    for (OpenedMat& m : p->mats) r.frs(m.ys, (uint64_t)m.npoints * m.width);
     r.frs(p->roots, nr);
     r.frs(p->final_poly, nf);
     p->pow_w = r.fr();
-    if (r.bad || nq > (len - r.off) / (32 * (p->w + q + p->wp))) throw LspError(LSP_E_ARG, "malformed proof bytes");
+    if (r.bad || nq > (len - r.off) / (32 * wsum)) throw LspError(LSP_E_ARG, "malformed proof bytes");
     p->queries.resize(nq);
     for (auto& qq : p->queries) {
-        r.frs(qq.trow, p->w);
-        r.frs(qq.tpath, r.u32());
-        r.frs(qq.qrow, q);
-        r.frs(qq.qpath, r.u32());
-        if (prep) {
-            r.frs(qq.prow, p->wp);
-            r.frs(qq.ppath, r.u32());
+        qq.open.resize(p->mats.size());
+        for (size_t m = 0; m < p->mats.size(); ++m) {
+            r.frs(qq.open[m].row, p->mats[m].width);
+            r.frs(qq.open[m].path, r.u32());
         }
         qq.sib.resize(nr);
         qq.fpath.resize(nr);
@@ -211,101 +186,109 @@ lsp_proof* deserialize(const uint8_t* buf, size_t len) {
 }
 
 namespace {
-// the flat arrays behind lsp_proof_view, built on first use and kept with the proof
+// the flat, query-major arrays behind both views, built on first use and kept
+// with the proof.  lsp_proof_view needs the first two matrices and the FRI openings
+// (`error`: what keeps them from being flat arrays), the preprocessed view the third
 struct Flat {
-    std::vector<Fr> single;  // trace_commit, quotient_commit, pow_witness
-    std::vector<Fr> trows, tpaths, qrows, qpaths, sibs, fpaths;
+    std::vector<Fr> single;  // the roots on the wire, pow_witness
+    struct Mat {
+        std::vector<Fr> rows, paths;
+        uint32_t path_len = 0;
+        bool uniform = true;
+    };
+    std::vector<Mat> mats;
+    std::vector<Fr> sibs, fpaths;
     std::vector<uint32_t> fri_path_lens;
-    uint32_t input_path_len = 0;
+    const char* error = nullptr;
 };
-// the same for lsp_proof_preprocessed_view (a cache of its own inside the proof's)
-struct PrepFlat {
-    std::vector<Fr> rows, paths;
-    uint32_t path_len = 0;
-};
-}  // namespace
 
-void proof_prep_view(const lsp_proof& p, lsp_proof_preprocessed_view* v) {
-    LSP_REQUIRE(p.wp != 0, LSP_E_STATE, "an LSPPRF02 proof has no preprocessed openings");
-    std::lock_guard<std::mutex> g(p.cache_mu);
-    if (!p.prep_view_cache) {
-        auto f = std::make_shared<PrepFlat>();
-        f->path_len = p.queries.empty() ? 0 : (uint32_t)p.queries[0].ppath.size();
-        LSP_REQUIRE(p.pl.size() == p.wp && p.pn.size() == p.wp, LSP_E_STATE, "preprocessed opened values missing");
-        for (auto& q : p.queries) {
-            if (q.prow.size() != p.wp || q.ppath.size() != f->path_len)
-                throw LspError(LSP_E_STATE, "proof queries are not uniform");
-            f->rows.insert(f->rows.end(), q.prow.begin(), q.prow.end());
-            f->paths.insert(f->paths.end(), q.ppath.begin(), q.ppath.end());
-        }
-        p.prep_view_cache = f;
-    }
-    const PrepFlat& f = *std::static_pointer_cast<PrepFlat>(p.prep_view_cache);
-    auto fr = [](const std::vector<Fr>& x) { return reinterpret_cast<const lsp_fr*>(x.data()); };
-    std::memset(v, 0, sizeof *v);
-    v->width = p.wp;
-    v->local = fr(p.pl);
-    v->next = fr(p.pn);
-    v->rows = fr(f.rows);
-    v->paths = fr(f.paths);
-    v->path_len = f.path_len;
-}
-
-void proof_view(const lsp_proof& p, lsp_proof_view* v) {
-    // built once, under the proof's cache mutex; never replaced afterwards, so
-    // pointers handed out stay valid until lsp_proof_free
-    std::lock_guard<std::mutex> g(p.cache_mu);
+// built once, under the proof's cache mutex (the caller holds it); never
+// replaced afterwards, so pointers handed out stay valid until lsp_proof_free
+const Flat& flat_of(const lsp_proof& p) {
     if (!p.view_cache) {
         auto f = std::make_shared<Flat>();
-        const size_t nq = p.queries.size(), nr = p.roots.size();
-        f->single = {p.troot, p.qroot, p.pow_w};
-        f->input_path_len = nq ? (uint32_t)p.queries[0].tpath.size() : 0;
+        const size_t nq = p.queries.size(), nr = p.roots.size(), nm = p.mats.size();
+        for (const OpenedMat& m : p.mats)
+            if (m.root_on_wire) f->single.push_back(m.root);
+        f->single.push_back(p.pow_w);
+        f->mats.resize(nm);
+        for (size_t m = 0; m < nm && nq; ++m) f->mats[m].path_len = (uint32_t)p.queries[0].open[m].path.size();
         f->fri_path_lens.assign(nr, 0);
-        if (nq && p.queries[0].fpath.size() != nr) throw LspError(LSP_E_STATE, "proof queries are not uniform");
-        for (size_t k = 0; k < nr && nq; ++k) f->fri_path_lens[k] = (uint32_t)p.queries[0].fpath[k].size();
+        for (size_t k = 0; k < nr && nq && p.queries[0].fpath.size() == nr; ++k)
+            f->fri_path_lens[k] = (uint32_t)p.queries[0].fpath[k].size();
         for (auto& q : p.queries) {
-            // the view holds one path length per tree (true of every proof
-            // this library makes: all matrices of a tree have one height)
-            if (q.tpath.size() != f->input_path_len || q.qpath.size() != f->input_path_len || q.sib.size() != nr ||
-                q.fpath.size() != nr || q.trow.size() != p.w || q.qrow.size() != p.qc.size())
-                throw LspError(LSP_E_STATE, "proof queries are not uniform");
-            for (size_t k = 0; k < nr; ++k)
-                if (q.fpath[k].size() != f->fri_path_lens[k]) throw LspError(LSP_E_STATE, "FRI paths differ in length");
-            f->trows.insert(f->trows.end(), q.trow.begin(), q.trow.end());
-            f->tpaths.insert(f->tpaths.end(), q.tpath.begin(), q.tpath.end());
-            f->qrows.insert(f->qrows.end(), q.qrow.begin(), q.qrow.end());
-            f->qpaths.insert(f->qpaths.end(), q.qpath.begin(), q.qpath.end());
+            for (size_t m = 0; m < nm; ++m) {
+                Flat::Mat& fm = f->mats[m];
+                const auto& o = q.open[m];
+                // the view holds one path length per tree (true of every proof
+                // this library makes: all matrices of a tree have one height)
+                if (o.row.size() != p.mats[m].width || o.path.size() != fm.path_len) fm.uniform = false;
+                fm.rows.insert(fm.rows.end(), o.row.begin(), o.row.end());
+                fm.paths.insert(fm.paths.end(), o.path.begin(), o.path.end());
+            }
+            if (f->error) continue;
+            if (!f->mats[MAT_TRACE].uniform || !f->mats[MAT_QUOTIENT].uniform ||
+                f->mats[MAT_QUOTIENT].path_len != f->mats[MAT_TRACE].path_len || q.sib.size() != nr ||
+                q.fpath.size() != nr) {
+                f->error = "proof queries are not uniform";
+                continue;
+            }
+            for (size_t k = 0; k < nr && !f->error; ++k)
+                if (q.fpath[k].size() != f->fri_path_lens[k]) f->error = "FRI paths differ in length";
             f->sibs.insert(f->sibs.end(), q.sib.begin(), q.sib.end());
             for (auto& fp : q.fpath) f->fpaths.insert(f->fpaths.end(), fp.begin(), fp.end());
         }
         p.view_cache = f;
     }
-    const Flat& f = *std::static_pointer_cast<Flat>(p.view_cache);
-    auto fr = [](const std::vector<Fr>& x) { return reinterpret_cast<const lsp_fr*>(x.data()); };
-    auto fr1 = [](const Fr& x) { return reinterpret_cast<const lsp_fr*>(&x); };
+    return *std::static_pointer_cast<Flat>(p.view_cache);
+}
+const lsp_fr* as_lsp(const std::vector<Fr>& x) { return reinterpret_cast<const lsp_fr*>(x.data()); }
+const lsp_fr* as_lsp(const Fr* x) { return reinterpret_cast<const lsp_fr*>(x); }
+}  // namespace
+
+void proof_prep_view(const lsp_proof& p, lsp_proof_preprocessed_view* v) {
+    LSP_REQUIRE(p.mats.size() > MAT_PREP, LSP_E_STATE, "an LSPPRF02 proof has no preprocessed openings");
+    std::lock_guard<std::mutex> g(p.cache_mu);
+    const Flat::Mat& f = flat_of(p).mats[MAT_PREP];
+    LSP_REQUIRE(f.uniform, LSP_E_STATE, "proof queries are not uniform");
+    const OpenedMat& m = p.mats[MAT_PREP];
+    std::memset(v, 0, sizeof *v);
+    v->width = m.width;
+    v->local = as_lsp(m.at(0));
+    v->next = as_lsp(m.at(1));
+    v->rows = as_lsp(f.rows);
+    v->paths = as_lsp(f.paths);
+    v->path_len = f.path_len;
+}
+
+void proof_view(const lsp_proof& p, lsp_proof_view* v) {
+    std::lock_guard<std::mutex> g(p.cache_mu);
+    const Flat& f = flat_of(p);
+    if (f.error) throw LspError(LSP_E_STATE, f.error);
+    const OpenedMat &t = p.mats[MAT_TRACE], &qm = p.mats[MAT_QUOTIENT];
     std::memset(v, 0, sizeof *v);
     v->degree_bits = p.log_h;
     v->log_quotient_chunks = p.log_q;
-    v->width = p.w;
+    v->width = t.width;
     v->num_queries = (uint32_t)p.queries.size();
     v->num_fri_rounds = (uint32_t)p.roots.size();
     v->final_poly_len = (uint32_t)p.final_poly.size();
-    v->input_path_len = f.input_path_len;
+    v->input_path_len = f.mats[MAT_TRACE].path_len;
     v->fri_path_lens = f.fri_path_lens.data();
-    v->trace_commit = fr1(f.single[0]);
-    v->quotient_commit = fr1(f.single[1]);
-    v->pow_witness = fr1(f.single[2]);
-    v->trace_local = fr(p.tl);
-    v->trace_next = fr(p.tn);
-    v->quotient_chunks = fr(p.qc);
-    v->fri_commits = fr(p.roots);
-    v->final_poly = fr(p.final_poly);
-    v->trace_rows = fr(f.trows);
-    v->trace_paths = fr(f.tpaths);
-    v->quotient_rows = fr(f.qrows);
-    v->quotient_paths = fr(f.qpaths);
-    v->fri_siblings = fr(f.sibs);
-    v->fri_paths = fr(f.fpaths);
+    v->trace_commit = as_lsp(&f.single[MAT_TRACE]);
+    v->quotient_commit = as_lsp(&f.single[MAT_QUOTIENT]);
+    v->pow_witness = as_lsp(&f.single.back());
+    v->trace_local = as_lsp(t.at(0));
+    v->trace_next = as_lsp(t.at(1));
+    v->quotient_chunks = as_lsp(qm.at(0));
+    v->fri_commits = as_lsp(p.roots);
+    v->final_poly = as_lsp(p.final_poly);
+    v->trace_rows = as_lsp(f.mats[MAT_TRACE].rows);
+    v->trace_paths = as_lsp(f.mats[MAT_TRACE].paths);
+    v->quotient_rows = as_lsp(f.mats[MAT_QUOTIENT].rows);
+    v->quotient_paths = as_lsp(f.mats[MAT_QUOTIENT].paths);
+    v->fri_siblings = as_lsp(f.sibs);
+    v->fri_paths = as_lsp(f.fpaths);
 }
 
 lsp_proof* proof_from_view(const lsp_proof_view& v) {
@@ -338,22 +321,25 @@ lsp_proof* proof_from_view(const lsp_proof_view& v) {
     auto p = std::make_unique<lsp_proof>();
     p->log_h = v.degree_bits;
     p->log_q = v.log_quotient_chunks;
-    p->w = v.width;
-    p->troot = rd(v.trace_commit, 1)[0];
-    p->qroot = rd(v.quotient_commit, 1)[0];
+    p->mats = {OpenedMat(MAT_TRACE, v.width), OpenedMat(MAT_QUOTIENT, (uint32_t)q)};
+    OpenedMat &t = p->mats[MAT_TRACE], &qm = p->mats[MAT_QUOTIENT];
+    t.root = rd(v.trace_commit, 1)[0];
+    qm.root = rd(v.quotient_commit, 1)[0];
     p->pow_w = rd(v.pow_witness, 1)[0];
-    p->tl = rd(v.trace_local, w);
-    p->tn = rd(v.trace_next, w);
-    p->qc = rd(v.quotient_chunks, q);
+    t.ys = rd(v.trace_local, w);
+    const std::vector<Fr> tn = rd(v.trace_next, w);
+    t.ys.insert(t.ys.end(), tn.begin(), tn.end());
+    qm.ys = rd(v.quotient_chunks, q);
     p->roots = nr ? rd(v.fri_commits, nr) : std::vector<Fr>();
     p->final_poly = rd(v.final_poly, v.final_poly_len);
     p->queries.resize(v.num_queries);
     for (size_t i = 0; i < v.num_queries; ++i) {
         auto& qq = p->queries[i];
-        qq.trow = rd(v.trace_rows + i * w, w);
-        qq.tpath = pl ? rd(v.trace_paths + i * pl, pl) : std::vector<Fr>();
-        qq.qrow = rd(v.quotient_rows + i * q, q);
-        qq.qpath = pl ? rd(v.quotient_paths + i * pl, pl) : std::vector<Fr>();
+        qq.open.resize(2);
+        qq.open[MAT_TRACE].row = rd(v.trace_rows + i * w, w);
+        qq.open[MAT_TRACE].path = pl ? rd(v.trace_paths + i * pl, pl) : std::vector<Fr>();
+        qq.open[MAT_QUOTIENT].row = rd(v.quotient_rows + i * q, q);
+        qq.open[MAT_QUOTIENT].path = pl ? rd(v.quotient_paths + i * pl, pl) : std::vector<Fr>();
         qq.sib = nr ? rd(v.fri_siblings + i * nr, nr) : std::vector<Fr>();
         qq.fpath.resize(nr);
         size_t o = i * fsum;

@@ -239,10 +239,19 @@ struct Prover {
     PhaseTimer T;
     std::unique_ptr<lsp_proof> proof;  // released to the caller by finish()
     std::vector<Fr> shifts;
-    // the trace: this rank's LDE rows, its subtree's layers, the host layers
-    // above the rank subtrees, h * coefficients (split or sub) read through tmap
-    Fr *lde = nullptr, *tlay = nullptr;
-    std::vector<std::vector<Fr>> ttop;
+    // One committed matrix as the opening walks it, in the order of proof->mats:
+    // this rank's LDE rows, its subtree's layers, the host layers above the rank
+    // subtrees (none: the layers hold every level), its width, its points
+    struct Committed {
+        const Fr* lde = nullptr;
+        Fr* layers = nullptr;
+        std::vector<std::vector<Fr>> top;
+        size_t width = 0;
+        uint32_t npoints = 0;
+    };
+    std::vector<Committed> mats;
+    // the trace's LDE, and h * coefficients (split or sub) read through tmap
+    Fr* lde = nullptr;
     const Fr* tcoef = nullptr;
     ColMap tmap;
     // the quotient.  G = 1: qv is the h x q chunk matrix.  G > 1: ranks g < Gq
@@ -250,18 +259,12 @@ struct Prover {
     // into a local buffer, whose inverse NTT goes to the slot)
     QuotientArgs qa;  // alpha set once sampled
     Fr *qv = nullptr, *stage = nullptr, *qloc = nullptr;
-    Fr *qlde = nullptr, *qlay = nullptr;
-    std::vector<std::vector<Fr>> qtop;
+    Fr* qlde = nullptr;
     // constraints before alpha: side work issued by the trace tree that the
     // main stream has not waited for yet (side_pending), see early_constraints
     bool early = false, side_pending = false;
     std::function<void(hipEvent_t)> side_fn;
-    Fr *inv_z = nullptr, *inv_zn = nullptr;  // 1 / (zeta - x), 1 / (zeta w_h - x) over this rank's rows
-    // the preprocessed matrix (one rank only): the tree's LDE and layers, all on
-    // the device, and its width (0: the proof has none)
-    const Fr *plde = nullptr, *play = nullptr;
-    size_t wp = 0;
-    Fr proot;
+    Fr* inv_z = nullptr;  // 1 / (zeta - x) over this rank's S rows, then 1 / (zeta w_h - x): one buffer, stride S
     // FRI: round 0's input, this rank's slice, at fvec[0, S) with the fold area
     // behind it; the commit phase (fri.cpp)
     Fr* fvec = nullptr;
@@ -277,14 +280,22 @@ struct Prover {
         ctx->spans.clear();
         proof->log_h = s.log_h;
         proof->log_q = s.log_q;
-        proof->w = (uint32_t)s.w;
         proof->rehearsal = comm.rehearsal();
+        add_matrix(s.w);
+        add_matrix(s.q);
         T.begin("prove");
     }
     Prover(const Prover&) = delete;  // side_fn points into this object
     // the main stream never runs ahead of side work it did not wait for
     ~Prover() {
         if (side_pending) (void)hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0);
+    }
+
+    // the next committed matrix, in this list and the proof's
+    Committed& add_matrix(size_t width) {
+        proof->mats.emplace_back(mats.size(), (uint32_t)width);
+        mats.push_back({nullptr, nullptr, {}, width, proof->mats.back().npoints});
+        return mats.back();
     }
 
     // the logical operations of p3_uni_stark::prove with their dims, worded as
@@ -306,12 +317,14 @@ struct Prover {
         trace_lde();
         quotient_setup();
         early_constraints();
-        tlay = ctx->fbuf("t_tree", TreeLayout{s.S}.size());
+        Committed& M = mats[MAT_TRACE];
+        M.lde = lde;
+        M.layers = ctx->fbuf("t_tree", TreeLayout{s.S}.size());
         T.begin("merkle tree");
-        proof->troot = shard_root(
-            ctx, comm, commit_device(ctx, one_mat(lde, (uint32_t)s.w), s.S, tlay, host_tree_top(ctx), nullptr,
+        proof->mats[MAT_TRACE].root = shard_root(
+            ctx, comm, commit_device(ctx, one_mat(lde, (uint32_t)s.w), s.S, M.layers, host_tree_top(ctx), nullptr,
                                early ? &side_fn : nullptr),
-            ttop, "trace subtree roots");
+            M.top, "trace subtree roots");
         T.end("merkle tree");
         T.end("commit to trace data");
     }
@@ -387,9 +400,9 @@ struct Prover {
         qa.row0_next = row0_next;
         qa.lde_rows = S;
         qa.lde_next_rows = lde_next ? S : 0;
-        if (wp && air.has_prog) {  // the same lrow / nrow of the preprocessed LDE
-            qa.prep = plde;
-            qa.wp = (uint32_t)wp;
+        if (mats.size() > MAT_PREP && air.has_prog) {  // the same lrow / nrow of the preprocessed LDE
+            qa.prep = mats[MAT_PREP].lde;
+            qa.wp = (uint32_t)mats[MAT_PREP].width;
         }
     }
 
@@ -478,16 +491,18 @@ struct Prover {
             lde_device(ctx, qv, h, q, s.lb, shifts.data(), qlde, s.k0, s.nk);
         }
         T.end("coset_lde_batch (quotient)");
-        qlay = ctx->fbuf("q_tree", TreeLayout{s.S}.size());
-        proof->qroot = shard_root(ctx, comm,
-                                  commit_device(ctx, one_mat(qlde, (uint32_t)q), s.S, qlay, host_tree_top(ctx)), qtop,
-                                  "quotient subtree roots");
+        Committed& M = mats[MAT_QUOTIENT];
+        M.lde = qlde;
+        M.layers = ctx->fbuf("q_tree", TreeLayout{s.S}.size());
+        proof->mats[MAT_QUOTIENT].root = shard_root(
+            ctx, comm, commit_device(ctx, one_mat(qlde, (uint32_t)q), s.S, M.layers, host_tree_top(ctx)), M.top,
+            "quotient subtree roots");
         T.end("commit to quotient poly chunks");
     }
 
     // ---- open: the trace at zeta and zeta w_h, the chunks at zeta
     void open_values(const Fr& zeta) {
-        const size_t h = s.h, w = s.w, q = s.q, S = s.S, row0 = s.row0;
+        const size_t h = s.h, S = s.S, row0 = s.row0;
         const uint32_t G = s.G, g = s.g, logN = s.logN;
         const Fr zeta_next = fr_mul(zeta, wh);
         T.begin("open");
@@ -500,41 +515,48 @@ struct Prover {
         // that evaluated no quotient points (g >= Gq), each over its first coset,
         // instead of all to rank 0; an allgather of the values replaces rank 0's
         // broadcast.  sub: the low coset's h / S ranks add partial sums.
-        // (with a preprocessed matrix: two more jobs, the matrix at zeta and at zeta*w_h)
-        const int nj = wp ? 5 : 3;
-        const size_t maxw = std::max({w, q, wp});
-        const size_t nsum = 2 * w + q + 2 * wp;
+        // The jobs are the (matrix, point) pairs in the list's order.
+        struct Job {
+            const Committed* m;
+            uint32_t point;
+            size_t off;  // of its sums among all the jobs'
+            bool here;
+        };
+        std::vector<Job> jobs;
+        size_t nsum = 0, maxw = 0;
+        const uint32_t nfree = G > s.Gq ? (uint32_t)(G - s.Gq) : 0u;
+        bool any_here = false;
+        for (const Committed& m : mats) {
+            maxw = std::max(maxw, m.width);
+            for (uint32_t p = 0; p < m.npoints; ++p, nsum += m.width) {
+                // sub: ranks 0 .. h/S - 1 hold the low coset's partial sums of every job
+                const uint32_t j = (uint32_t)jobs.size();
+                const bool here = s.sub ? row0 < h : g == (nfree ? G - 1 - j % nfree : G - 1 - j % G);
+                jobs.push_back({&m, p, nsum, here});
+                any_here = any_here || here;
+            }
+        }
         Fr* sums = ctx->fbuf("o_sums", nsum);
         const size_t nlow = std::min(S, h);  // this rank's rows of one coset
-        const size_t joff[5] = {0, w, 2 * w, 2 * w + q, 2 * w + q + wp}, jw[5] = {w, w, q, wp, wp};
-        bool job_here[5] = {false, false, false, false, false};
-        if (s.sub) {
-            job_here[0] = job_here[1] = job_here[2] = row0 < h;  // ranks 0 .. h/S - 1: the low coset's partial sums
-        } else {
-            const uint32_t nfree = G > s.Gq ? (uint32_t)(G - s.Gq) : 0u;
-            for (int j = 0; j < nj; ++j)
-                job_here[j] = g == (nfree ? G - 1 - (uint32_t)j % nfree : G - 1 - (uint32_t)j % G);
-        }
-        if (job_here[0] || job_here[1] || job_here[2]) {
+        if (any_here) {
             ctx->fbuf("o_partial", ((nlow + 1023) / 1024) * maxw);  // the drivers' scratch, sized once for the widest job
-            const Fr* jm[5] = {lde, lde, qlde, plde, plde};
-            const Fr* jinv[5] = {inv_z, inv_zn, inv_z, inv_z, inv_zn};
-            for (int j = 0; j < nj; ++j)
-                if (job_here[j])
-                    barycentric_sums(ctx, jm[j], (uint32_t)jw[j], nlow, jinv[j], GEN, logN, row0, sums + joff[j]);
+            for (const Job& j : jobs)
+                if (j.here)
+                    barycentric_sums(ctx, j.m->lde, (uint32_t)j.m->width, nlow, inv_z + j.point * S, GEN, logN, row0,
+                                     sums + j.off);
         }
         Fr* hs = (Fr*)ctx->hbuf("o_sums_h", nsum * sizeof(Fr));  // pinned
-        if (job_here[0] || job_here[1] || job_here[2]) {
+        if (any_here) {
             LSP_HIP(hipMemcpyAsync(hs, sums, nsum * sizeof(Fr), hipMemcpyDeviceToHost, st));
             LSP_HIP(hipStreamSynchronize(st));
         }
         // the coset of this rank's first rows: c = GEN w_N^bitrev(row0) (sub: the low coset, GEN)
         const Fr cpos = s.sub ? GEN : fr_mul(GEN, fr_pow_u64(host_two_adic_generator(logN), host_bitrev(row0, logN)));
         const CosetFactor factor(cpos, h, true);
-        const Fr jz[5] = {zeta, zeta_next, zeta, zeta, zeta_next};
-        for (int j = 0; j < nj; ++j) {
-            const Fr f = factor.at(jz[j]);
-            for (size_t k = 0; k < jw[j]; ++k) hs[joff[j] + k] = job_here[j] ? fr_mul(hs[joff[j] + k], f) : fr_zero();
+        const Fr z[2] = {zeta, zeta_next};
+        for (const Job& j : jobs) {
+            const Fr f = factor.at(z[j.point]);
+            for (size_t k = 0; k < j.m->width; ++k) hs[j.off + k] = j.here ? fr_mul(hs[j.off + k], f) : fr_zero();
         }
         if (G > 1) {  // every value from its job's rank(s): the sum over ranks
             const std::vector<Fr> all = comm.allgather_fr(ctx, hs, nsum, "opened values");
@@ -544,12 +566,10 @@ struct Prover {
                 hs[k] = acc;
             }
         }
-        proof->tl.assign(hs, hs + w);
-        proof->tn.assign(hs + w, hs + 2 * w);
-        proof->qc.assign(hs + 2 * w, hs + 2 * w + q);
-        if (wp) {
-            proof->pl.assign(hs + joff[3], hs + joff[3] + wp);
-            proof->pn.assign(hs + joff[4], hs + joff[4] + wp);
+        const Fr* y = hs;  // a matrix's jobs lie back to back: its opened values per point
+        for (OpenedMat& m : proof->mats) {
+            m.ys.assign(y, y + (size_t)m.npoints * m.width);
+            y += m.ys.size();
         }
         T.end("compute opened values with Lagrange interpolation");
     }
@@ -559,8 +579,8 @@ struct Prover {
         const size_t S = s.S, row0 = s.row0;
         const uint32_t logN = s.logN;
         T.begin("compute_inverse_denominators");
-        inv_z = ctx->fbuf("o_invz", S);
-        inv_zn = ctx->fbuf("o_invzn", S);
+        inv_z = ctx->fbuf("o_invz", 2 * S);
+        Fr* const inv_zn = inv_z + S;
         // this rank's rows are the coset c H_S (c = GEN w_N^bitrev(row0)), so the
         // product of its denominators is prod (zeta - c w) = zeta^S - c^S: its
         // inverse on the host replaces the batch inverse's Fermat chain on the GPU
@@ -592,12 +612,13 @@ struct Prover {
         span("reduce matrix quotient", w, s.N, -1);
         span("reduce matrix quotient", w, s.N, -1);
         for (size_t j = 0; j < q; ++j) span("reduce matrix quotient", 1, s.N, -1);
+        const OpenedMat &tm = proof->mats[MAT_TRACE], &qm = proof->mats[MAT_QUOTIENT];
         std::vector<Fr> apw = alpha_powers(alpha_fri, 2 * w + q);
-        const Fr ry_z = reduce_opened(apw.data(), proof->tl.data(), w);
-        const Fr ry_zn = reduce_opened(apw.data(), proof->tn.data(), w);
+        const Fr ry_z = reduce_opened(apw.data(), tm.at(0), w);
+        const Fr ry_zn = reduce_opened(apw.data(), tm.at(1), w);
         Fr* dapw = ctx->fbuf("o_apw", apw.size() + q);
         const size_t napw = apw.size();
-        apw.insert(apw.end(), proof->qc.begin(), proof->qc.end());
+        apw.insert(apw.end(), qm.ys.begin(), qm.ys.end());
         ctx->h2d_async("o_apw_h", dapw, apw.data(), apw.size() * sizeof(Fr));
         fvec = ctx->fbuf("f_vec", 2 * s.S);
         ReduceArgs ra;
@@ -606,7 +627,7 @@ struct Prover {
         ra.qlde = qlde;
         ra.q = (uint32_t)q;
         ra.inv_z = inv_z;
-        ra.inv_zn = inv_zn;
+        ra.inv_zn = inv_z + s.S;
         ra.apw = dapw;
         ra.ry_z = ry_z;
         ra.ry_zn = ry_zn;
@@ -617,32 +638,16 @@ struct Prover {
         if (const size_t nsc = reduce_rows_scratch(ra.w, ra.q, ra.lds_max))  // constants beyond the LDS: global
             ra.consts29 = (F29*)ctx->buf("o_rr_consts", nsc * sizeof(F29));
         LSP_HIP(launch_reduce_rows(ra, st));
-        if (wp) reduce_prep(alpha_fri, 2 * w + q);
+        // the matrices after the fused pair (the preprocessed one), each at zeta
+        // and zeta*w_h, continue the running power: accumulated into fvec
+        Fr off = fr_pow_u64(alpha_fri, 2 * w + q);
+        for (size_t m = MAT_QUOTIENT + 1; m < mats.size(); ++m) {
+            span("reduce matrix preprocessed at zeta", mats[m].width, s.N, -1);
+            span("reduce matrix preprocessed at zeta*w", mats[m].width, s.N, -1);
+            reduce_matrix(ctx, mats[m].lde, s.S, mats[m].width, inv_z, proof->mats[m].ys.data(), mats[m].npoints,
+                          alpha_fri, off, fvec, "o_apw_prep");
+        }
         T.end("reduce rows");
-    }
-
-    // the preprocessed matrix as a third matrix at zeta and zeta*w_h, continuing
-    // the running power from alpha_fri^done: accumulated into fvec
-    void reduce_prep(const Fr& alpha_fri, size_t done) {
-        span("reduce matrix preprocessed at zeta", wp, s.N, -1);
-        span("reduce matrix preprocessed at zeta*w", wp, s.N, -1);
-        const std::vector<Fr> apw = alpha_powers(alpha_fri, wp);
-        Fr* dapw = ctx->fbuf("o_apw_prep", wp);
-        ctx->h2d_async("o_apw_prep_h", dapw, apw.data(), wp * sizeof(Fr));
-        PrepReduceArgs pa;
-        pa.prep = plde;
-        pa.wp = (uint32_t)wp;
-        pa.inv_z = inv_z;
-        pa.inv_zn = inv_zn;
-        pa.apw = dapw;
-        pa.ry_z = reduce_opened(apw.data(), proof->pl.data(), wp);
-        pa.ry_zn = reduce_opened(apw.data(), proof->pn.data(), wp);
-        pa.off_z = fr_pow_u64(alpha_fri, done);
-        pa.off_zn = fr_pow_u64(alpha_fri, done + wp);
-        pa.out = fvec;
-        pa.n = s.S;
-        pa.lds_max = ctx->lds_per_block;
-        LSP_HIP(launch_reduce_prep(pa, st));
     }
 
     // ---- FRI commit phase (fri.cpp): no roll-in; the host takes the tree tops
@@ -669,9 +674,10 @@ struct Prover {
     void query_phase(const std::vector<size_t>& idxs) {
         q1 = host_clock::now();
         const uint32_t nq = (uint32_t)idxs.size();
-        size_t E = s.w + s.logS + s.q + s.logS;  // elements per query below the rank subtrees
-        if (wp) E += wp + s.logS;                // the preprocessed row and its whole path (one rank: logS = logN)
-        E += fri->query_elems();
+        // elements per query below the rank subtrees: per matrix its row and path
+        // (one rank: logS = logN, the whole path), then the FRI openings
+        size_t E = fri->query_elems();
+        for (const Committed& m : mats) E += m.width + s.logS;
         std::vector<uint64_t> ptrs;
         std::vector<uint32_t> mine;
         query_pointers(idxs, ptrs, mine);
@@ -704,20 +710,14 @@ struct Prover {
 
     // the addresses of this rank's queries' openings (E per query), and which queries they are
     void query_pointers(const std::vector<size_t>& idxs, std::vector<uint64_t>& ptrs, std::vector<uint32_t>& mine) {
-        const size_t w = s.w, q = s.q, S = s.S;
         for (uint32_t qi = 0; qi < idxs.size(); ++qi) {
             const size_t idx = idxs[qi];
             if ((idx >> s.logS) != s.g) continue;
             mine.push_back(qi);
             const size_t li = idx - s.row0;
-            auto P = [&](const Fr* p) { ptrs.push_back((uint64_t)(uintptr_t)p); };
-            for (size_t c = 0; c < w; ++c) P(lde + li * w + c);
-            push_path(ptrs, tlay, S, li);
-            for (size_t j = 0; j < q; ++j) P(qlde + li * q + j);
-            push_path(ptrs, qlay, S, li);
-            if (wp) {  // (one rank: li = idx, S = N, the tree's layers hold every level)
-                for (size_t c = 0; c < wp; ++c) P(plde + li * wp + c);
-                push_path(ptrs, play, S, li);
+            for (const Committed& m : mats) {
+                for (size_t c = 0; c < m.width; ++c) ptrs.push_back((uint64_t)(uintptr_t)(m.lde + li * m.width + c));
+                push_path(ptrs, m.layers, s.S, li);
             }
             fri->push_query(ptrs, idx);
         }
@@ -726,7 +726,7 @@ struct Prover {
     // each query's record is independent: assembled (and serialized)
     // on the host pool -- ~0.1 + 0.2 ms of one thread's time at 2^19
     void query_records(const std::vector<size_t>& idxs, const Fr* opened, size_t E) {
-        const size_t w = s.w, q = s.q, nq = idxs.size();
+        const size_t nq = idxs.size();
         const uint32_t logS = s.logS, nr = (uint32_t)fri->rounds.size();
         auto top_path = [&](const std::vector<std::vector<Fr>>& top, size_t sub, std::vector<Fr>& out) {
             for (uint32_t i = 0; i + 1 < top.size(); ++i) out.push_back(top[i][(sub >> i) ^ 1]);
@@ -744,21 +744,14 @@ struct Prover {
             qq.sib.clear();
             qq.sib.reserve(nr);
             qq.fpath.resize(nr);
-            qq.trow.assign(e, e + w);
-            e += w;
-            qq.tpath.assign(e, e + logS);
-            e += logS;
-            top_path(ttop, o, qq.tpath);
-            qq.qrow.assign(e, e + q);
-            e += q;
-            qq.qpath.assign(e, e + logS);
-            e += logS;
-            top_path(qtop, o, qq.qpath);
-            if (wp) {
-                qq.prow.assign(e, e + wp);
-                e += wp;
-                qq.ppath.assign(e, e + logS);
+            qq.open.resize(mats.size());
+            for (size_t m = 0; m < mats.size(); ++m) {
+                lsp_query::Opening& op = qq.open[m];
+                op.row.assign(e, e + mats[m].width);
+                e += mats[m].width;
+                op.path.assign(e, e + logS);
                 e += logS;
+                top_path(mats[m].top, o, op.path);  // (no host layers: the tree's own hold every level)
             }
             for (uint32_t r = 0; r < nr; ++r) {
                 const FriRound& R = fri->rounds[r];
@@ -808,13 +801,14 @@ lsp_proof* prove_shard(lsp_ctx* ctx, Comm& comm, const Fr* d_trace, size_t h, si
         LSP_REQUIRE(prep->ctx == ctx, LSP_E_ARG, "the preprocessed tree belongs to another context");
         LSP_REQUIRE(prep->height == geo.N && prep->mats.size() == 1 && wp >= 1, LSP_E_ARG,
                     "the preprocessed tree is not over one matrix of height h << log_blowup");
-        LSP_REQUIRE(reduce_prep_fits((uint32_t)wp, ctx->lds_per_block), LSP_E_ARG,
+        LSP_REQUIRE(reduce_matrix_scratch((uint32_t)wp, ctx->lds_per_block) == 0, LSP_E_ARG,
                     "the preprocessed matrix is wider than the reduce kernel's LDS holds");
-        P.plde = prep->mats[0];
-        P.play = prep->layers;
-        P.wp = wp;
-        P.proof->wp = (uint32_t)wp;
-        P.proot = d2h_fr(ctx, prep->layers + TreeLayout{geo.N}.root());
+        // the third committed matrix: the tree's LDE and layers, all on the
+        // device; its root is the verifier's own input
+        auto& M = P.add_matrix(wp);
+        M.lde = prep->mats[0];
+        M.layers = prep->layers;
+        P.proof->mats[MAT_PREP].root = d2h_fr(ctx, prep->layers + TreeLayout{geo.N}.root());
     }
 
     P.commit_trace();
@@ -822,28 +816,24 @@ lsp_proof* prove_shard(lsp_ctx* ctx, Comm& comm, const Fr* d_trace, size_t h, si
     const TranscriptCfg& TC = ctx->transcript;
     Challenger ch(&ctx->p2, TC.mont_bits);
     if (TC.log_degree) ch.observe(fr_from_u64(geo.log_h));
-    ch.observe(P.proof->troot);
-    if (prep) ch.observe(P.proot);  // U13
+    ch.observe(P.proof->mats[MAT_TRACE].root);
+    if (prep) ch.observe(P.proof->mats[MAT_PREP].root);  // U13
     if (TC.public_values)
         for (size_t i = 0; i < npub; ++i) ch.observe(pub[i]);
     const Fr alpha = ch.sample();
 
     P.quotient(alpha);
     P.commit_quotient();
-    ch.observe(P.proof->qroot);
+    ch.observe(P.proof->mats[MAT_QUOTIENT].root);
     const Fr zeta = ch.sample();
 
     // alpha_fri is sampled once the opened values exist: U7 may observe them
     // first; the default samples it right after zeta, and nothing touches the
     // transcript in between
     P.open_values(zeta);
-    if (TC.opened_values) {  // U7: every opened value, in (matrix, point) order, before alpha_fri
-        for (const Fr& v : P.proof->tl) ch.observe(v);
-        for (const Fr& v : P.proof->tn) ch.observe(v);
-        for (const Fr& v : P.proof->qc) ch.observe(v);
-        for (const Fr& v : P.proof->pl) ch.observe(v);
-        for (const Fr& v : P.proof->pn) ch.observe(v);
-    }
+    if (TC.opened_values)  // U7: every opened value, in (matrix, point) order, before alpha_fri
+        for (const OpenedMat& m : P.proof->mats)
+            for (const Fr& v : m.ys) ch.observe(v);
     const Fr alpha_fri = ch.sample();
 
     P.reduce_rows(alpha_fri);

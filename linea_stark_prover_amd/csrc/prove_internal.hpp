@@ -63,6 +63,11 @@ void fri_fold(lsp_ctx* ctx, const FoldSpec& f, size_t m);
 // alpha^k, k < n, and a row of opened values reduced by them: sum_c apw[c] ys[c], c < w
 std::vector<Fr> alpha_powers(const Fr& alpha, size_t n);
 Fr reduce_opened(const Fr* apw, const Fr* ys, size_t w);
+// One matrix's terms of a reduced opening, added to ro (device, n): the n x w
+// device matrix M at npts >= 1 points, inv[p n + i] its inverse denominators
+// (device), ys[p w + c] its opened values (host).  off: as apow below; buffers named after `tag`
+void reduce_matrix(lsp_ctx* ctx, const Fr* M, size_t n, size_t w, const Fr* inv, const Fr* ys, size_t npts,
+                   const Fr& alpha, Fr& off, Fr* ro, const std::string& tag);
 // ---- Merkle trees
 // Where a tree's digests live in its one array, leaves first: level l (the
 // leaves are level 0) holds leaves >> l nodes from offset(l) on.
@@ -244,6 +249,23 @@ const Fr* gather_to_host(lsp_ctx* ctx, const std::vector<uint64_t>& ptrs);
 // rolls in at height 2^l or nullptr; sib / path_len / path(k, l): round k's
 // opening, called in wire order -- and the final polynomial; 0, 10 or 11
 Fr fold_row(size_t index, uint32_t log_height, const Fr& beta, const Fr& e0, const Fr& e1);
+// One matrix's term of a query's reduced opening at the LDE point x (both
+// verifiers): over its points p and columns c,
+// apow alpha^(p w + c) (row[c] - ys[p w + c]) / (x - zs[p]).  apow, the running
+// power of alpha, leaves multiplied by alpha^(npts w).
+inline Fr reduced_opening_term(const Fr* row, const Fr* ys, size_t w, const Fr* zs, size_t npts, const Fr& x,
+                               const Fr& alpha, Fr& apow) {
+    Fr term = fr_zero();
+    for (size_t p = 0; p < npts; ++p) {
+        Fr s = fr_zero();
+        for (size_t c = 0; c < w; ++c) {
+            s = fr_add(s, fr_mul(apow, fr_sub(row[c], ys[p * w + c])));
+            apow = fr_mul(apow, alpha);
+        }
+        term = fr_add(term, fr_mul(s, fr_inv(fr_sub(x, zs[p]))));
+    }
+    return term;
+}
 int fri_replay(Challenger& ch, const lsp_ctx* ctx, const std::vector<Fr>& roots, const std::vector<Fr>& final_poly,
                const Fr& pow_w, std::vector<Fr>& betas);
 int fri_check_query(const P2Host& p2, const std::vector<Fr>& roots, const std::vector<Fr>& betas,

@@ -141,4 +141,25 @@ Fr reduce_opened(const Fr* apw, const Fr* ys, size_t w) {
     return ry;
 }
 
+void reduce_matrix(lsp_ctx* ctx, const Fr* M, size_t n, size_t w, const Fr* inv, const Fr* ys, size_t npts,
+                   const Fr& alpha, Fr& off, Fr* ro, const std::string& tag) {
+    // for the kernel: alpha^c (c < w), then per point the running power, then
+    // per point that power times the opened values reduced by the alpha^c
+    std::vector<Fr> coef = alpha_powers(alpha, w + 1);
+    const Fr aw = coef[w];  // alpha^w: the running power advances by the matrix width
+    coef.resize(w + 2 * npts);
+    for (size_t p = 0; p < npts; ++p) {
+        coef[w + p] = off;
+        coef[w + npts + p] = fr_mul(off, reduce_opened(coef.data(), ys + p * w, w));
+        off = fr_mul(off, aw);
+    }
+    Fr* dc = ctx->fbuf(tag, coef.size());
+    ctx->h2d_async(tag + "_h", dc, coef.data(), coef.size() * sizeof(Fr));
+    F29* consts29 = nullptr;  // alpha powers beyond the LDS: global
+    if (const size_t nsc = reduce_matrix_scratch((uint32_t)w, ctx->lds_per_block))
+        consts29 = (F29*)ctx->buf(tag + "_29", nsc * sizeof(F29));
+    LSP_HIP(launch_reduce_matrix(M, n, (uint32_t)w, dc, (uint32_t)npts, inv, dc + w, dc + w + npts, ro,
+                                 ctx->lds_per_block, consts29, ctx->stream));
+}
+
 }  // namespace lsp

@@ -16,17 +16,18 @@ bool mk_verify(const P2Host& p2, const Fr& root, size_t index, const Fr* leaf, s
     const Fr got = merkle_path_root(p2, p2.hash(leaf, nleaf), index, pl, [&](uint32_t) { return r.fr(); }, no_injection);
     return !r.bad && fr_eq(got, root);
 }
+// the check a committed matrix's query opening fails (host.hpp MAT_*)
+constexpr int OPENING_CHECK[] = {8, 9, 14};
 }  // namespace
 
 // prep_commit (optional) with prep_width: the verifier's own data about the
 // AIR's preprocessed matrix (p3's VerifierData), never proof fields.  Such a
-// proof is "LSPPRF03": LSPPRF02 with u32 prep_width after final_poly_len,
-// prep@zeta[wp] and prep@zeta*w[wp] after chunks@zeta[q], and per query, after
-// the quotient row and path, the preprocessed row[wp] and u32 len + path.  The
-// root is observed after the trace root (U13), the opened values after the
-// chunks', and the FRI input continues the running alpha_fri power with the
-// matrix at zeta, then at zeta*w.  Each format is rejected where the other is
-// expected.
+// proof is "LSPPRF03": the list of committed matrices (host.hpp) is one longer,
+// and everything below walks that list -- the header's width, the opened values
+// (observed in its order), each query's openings and the FRI input, where the
+// running alpha_fri power goes through every matrix at each of its points.  The
+// preprocessed root is observed after the trace root (U13).  Each format is
+// rejected where the other is expected.
 int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, const uint8_t* b, size_t n,
                 const Fr* prep_commit, uint32_t prep_width) {
     if (npub < 2) return 1;
@@ -43,14 +44,21 @@ int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, 
     if (nr != logN - lb - ctx->log_final_poly_len || nf != (1u << ctx->log_final_poly_len)) return 4;
     const size_t q = (size_t)1 << log_q, h = (size_t)1 << log_h;
     const size_t flen = (size_t)1 << ctx->log_final_poly_len;
-    const Fr troot = r.fr(), qroot = r.fr();
-    if (r.n - r.off < ((size_t)2 * w + q + 2 * (size_t)wp) * 32) return 5;  // (before any allocation by a claimed width)
-    std::vector<Fr> tl(w), tn(w), qc(q), pl(wp), pn(wp), roots(nr), betas, fp(flen);
-    for (auto& x : tl) x = r.fr();
-    for (auto& x : tn) x = r.fr();
-    for (auto& x : qc) x = r.fr();
-    for (auto& x : pl) x = r.fr();
-    for (auto& x : pn) x = r.fr();
+    const uint32_t widths[] = {w, (uint32_t)q, wp};
+    std::vector<OpenedMat> mats;
+    size_t nys = 0, maxw = 0;
+    for (size_t m = 0; m < (prep_commit ? 3u : 2u); ++m) {
+        mats.emplace_back(m, widths[m]);
+        mats[m].root = mats[m].root_on_wire ? r.fr() : *prep_commit;
+        nys += (size_t)mats[m].npoints * widths[m];
+        maxw = std::max<size_t>(maxw, widths[m]);
+    }
+    if (r.n - r.off < nys * 32) return 5;  // (before any allocation by a claimed width)
+    std::vector<Fr> roots(nr), betas, fp(flen);
+    for (OpenedMat& m : mats) {
+        m.ys.resize((size_t)m.npoints * m.width);
+        for (auto& x : m.ys) x = r.fr();
+    }
     for (auto& x : roots) x = r.fr();
     for (auto& x : fp) x = r.fr();
     const Fr pw = r.fr();
@@ -59,58 +67,32 @@ int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, 
     const TranscriptCfg& TC = ctx->transcript;  // U7 / U8 / U12, as the prover
     Challenger ch(&ctx->p2, TC.mont_bits);
     if (TC.log_degree) ch.observe(fr_from_u64(log_h));
-    ch.observe(troot);
-    if (prep_commit) ch.observe(*prep_commit);  // U13
+    ch.observe(mats[MAT_TRACE].root);
+    for (const OpenedMat& m : mats)
+        if (!m.root_on_wire) ch.observe(m.root);  // U13: the verifier's own commitments
     if (TC.public_values)
         for (size_t i = 0; i < npub; ++i) ch.observe(pub[i]);
     const Fr alpha = ch.sample();
-    ch.observe(qroot);
+    ch.observe(mats[MAT_QUOTIENT].root);
     const Fr zeta = ch.sample();
     const Fr wh = host_two_adic_generator(log_h), wh_inv = fr_inv(wh);
-    const Fr zeta_next = fr_mul(zeta, wh);
-    if (TC.opened_values) {
-        for (const Fr& v : tl) ch.observe(v);
-        for (const Fr& v : tn) ch.observe(v);
-        for (const Fr& v : qc) ch.observe(v);
-        for (const Fr& v : pl) ch.observe(v);
-        for (const Fr& v : pn) ch.observe(v);
-    }
+    const Fr points[2] = {zeta, fr_mul(zeta, wh)};
+    if (TC.opened_values)
+        for (const OpenedMat& m : mats)
+            for (const Fr& v : m.ys) ch.observe(v);
     const Fr alpha_fri = ch.sample();
     if (const int bad = fri_replay(ch, ctx, roots, fp, pw, betas)) return bad;
     const Fr gN = host_two_adic_generator(logN);
-    std::vector<Fr> trow(w), qrow(q), prow(wp);
+    std::vector<Fr> row(maxw);
     for (uint32_t qi = 0; qi < nq; ++qi) {
         const size_t idx = (size_t)ch.sample_bits(logN);
-        for (auto& x : trow) x = r.fr();
-        if (!mk_verify(ctx->p2, troot, idx, trow.data(), w, r, logN)) return 8;
-        for (auto& x : qrow) x = r.fr();
-        if (!mk_verify(ctx->p2, qroot, idx, qrow.data(), q, r, logN)) return 9;
-        if (prep_commit) {
-            for (auto& x : prow) x = r.fr();
-            if (!mk_verify(ctx->p2, *prep_commit, idx, prow.data(), wp, r, logN)) return 14;
-        }
         const Fr x = fr_mul(GEN, fr_pow_u64(gN, host_bitrev(idx, logN)));
-        const Fr dz = fr_inv(fr_sub(x, zeta)), dzn = fr_inv(fr_sub(x, zeta_next));
         Fr ro = fr_zero(), apow = one;
-        for (uint32_t c = 0; c < w; ++c) {
-            ro = fr_add(ro, fr_mul(apow, fr_mul(fr_sub(trow[c], tl[c]), dz)));
-            apow = fr_mul(apow, alpha_fri);
-        }
-        for (uint32_t c = 0; c < w; ++c) {
-            ro = fr_add(ro, fr_mul(apow, fr_mul(fr_sub(trow[c], tn[c]), dzn)));
-            apow = fr_mul(apow, alpha_fri);
-        }
-        for (size_t j = 0; j < q; ++j) {
-            ro = fr_add(ro, fr_mul(apow, fr_mul(fr_sub(qrow[j], qc[j]), dz)));
-            apow = fr_mul(apow, alpha_fri);
-        }
-        for (uint32_t c = 0; c < wp; ++c) {
-            ro = fr_add(ro, fr_mul(apow, fr_mul(fr_sub(prow[c], pl[c]), dz)));
-            apow = fr_mul(apow, alpha_fri);
-        }
-        for (uint32_t c = 0; c < wp; ++c) {
-            ro = fr_add(ro, fr_mul(apow, fr_mul(fr_sub(prow[c], pn[c]), dzn)));
-            apow = fr_mul(apow, alpha_fri);
+        for (size_t m = 0; m < mats.size(); ++m) {
+            const OpenedMat& M = mats[m];
+            for (uint32_t c = 0; c < M.width; ++c) row[c] = r.fr();
+            if (!mk_verify(ctx->p2, M.root, idx, row.data(), M.width, r, logN)) return OPENING_CHECK[m];
+            ro = fr_add(ro, reduced_opening_term(row.data(), M.ys.data(), M.width, points, M.npoints, x, alpha_fri, apow));
         }
         // the commit-phase openings, read from the stream as the chain asks for them
         const int bad = fri_check_query(
@@ -126,6 +108,7 @@ int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, 
     sh[0] = GEN;
     for (size_t j = 1; j < q; ++j) sh[j] = fr_mul(sh[j - 1], gQ);
     auto zp = [&](const Fr& s, const Fr& xx) { return fr_sub(fr_pow_u64(fr_mul(xx, fr_inv(s)), h), one); };
+    const Fr* qc = mats[MAT_QUOTIENT].at(0);
     Fr quotient = fr_zero();
     for (size_t i = 0; i < q; ++i) {
         Fr prod = one;
@@ -138,7 +121,9 @@ int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, 
     const Fr last = fr_mul(zh, fr_inv(fr_sub(zeta, wh_inv)));
     const Fr trans = fr_sub(zeta, wh_inv);
     Fr acc = fr_zero();
-    air.eval_fold(tl.data(), tn.data(), pub, first, last, trans, alpha, acc, pl.data(), pn.data());
+    const OpenedMat &T = mats[MAT_TRACE], &P = mats.back();  // (P: read only when it is the preprocessed matrix)
+    air.eval_fold(T.at(0), T.at(1), pub, first, last, trans, alpha, acc, prep_commit ? P.at(0) : nullptr,
+                  prep_commit ? P.at(1) : nullptr);
     if (!fr_eq(fr_mul(acc, fr_inv(zh)), quotient)) return 13;
     return 0;
 }

@@ -174,3 +174,59 @@ def test_trivial_end_groups(red):
     assert max(a) < 1 << 31
     b = [(1 << 30) - 2 + L32[i] for i in range(8)]
     assert max(b) < 1 << 31
+
+
+def f29_from_fr(x):
+    """fr29.hpp f29_from_fr: the word times 2^5, reduced below 2 r"""
+    return f29_reduce(limbs(x << 5))
+
+
+def reduce_matrix_row(row, apw, off, offys, inv, old):
+    """One row of k_reduce_matrix (k_open.hip) on 256-bit words, every bound of
+    its comment asserted: RR_CHUNK = 3 products per lazy row sum, MR_POINTS = 2
+    terms per lazy point sum.  Returns the limbs written back (below 2 r)."""
+    rr = [0] * 9
+    for k in range(0, len(row), 3):
+        s = rr
+        for x, a in zip(row[k:k + 3], apw[k:k + 3]):
+            t, _ = f29_mul(limbs(x), f29_from_fr(a))
+            assert val(t) < 8.07 * R and max(t[:8]) <= MASK
+            s = [u + v for u, v in zip(s, t)]
+        assert val(s) < 26.3 * R and max(s[:8]) < 1 << 31
+        rr = f29_reduce_qt(s)
+        assert val(rr) < 2 * R
+    acc = limbs(old)
+    for p in range(0, len(off), 2):
+        s = acc
+        for o, oy, iv in zip(off[p:p + 2], offys[p:p + 2], inv[p:p + 2]):
+            t, _ = f29_mul(rr, f29_from_fr(o))
+            assert val(t) < 8.01 * R and max(t[:8]) <= MASK
+            d = [a + L16[i] - b for i, (a, b) in enumerate(zip(limbs(oy), t))]
+            assert min(d) >= 0 and max(d[:8]) < 3 << 29 and val(d) < 29.72 * R
+            u, _ = f29_mul(d, f29_from_fr(iv))  # (asserts every column sum below 2^64)
+            assert val(u) < 8.14 * R and max(u[:8]) <= MASK
+            s = [a + b for a, b in zip(s, u)]
+        assert val(s) < 30 * R and max(s[:8]) < 3 << 29
+        acc = f29_reduce_qt(s)
+        assert val(acc) < 2 * R and max(acc[:8]) <= MASK
+    return acc
+
+
+@pytest.mark.parametrize("npts", [1, 2, 3, 4, 5])
+def test_reduce_matrix_sum_shape(npts):
+    """k_reduce_matrix on any 256-bit words (lsp_open_reduce passes a caller's
+    on): the lazy sums stay inside f29_reduce_qt's bounds for any number of
+    points, and the value is the formula's (words in the 2^256 form)"""
+    rng = random.Random(23 + npts)
+    top = (1 << 256) - 1
+    i256 = pow(2, -256, R)
+    for trial in range(40):
+        w = rng.choice([1, 2, 3, 4, 7])
+        draw = (lambda: top) if trial == 0 else (lambda: rng.choice([top, R - 1, rng.randrange(1 << 256)]))
+        row, apw = [draw() for _ in range(w)], [draw() for _ in range(w)]
+        off, offys, inv = ([draw() for _ in range(npts)] for _ in range(3))
+        old = draw()
+        got = reduce_matrix_row(row, apw, off, offys, inv, old)
+        rr = sum(x * a for x, a in zip(row, apw)) * i256
+        want = old + sum((oy - o * rr * i256) * iv * i256 for o, oy, iv in zip(off, offys, inv))
+        assert val(got) % R == want % R

@@ -315,7 +315,7 @@ def test_unfit_trees_are_refused(gpu_ctx):
     assert proof == gpu_ctx.prove(trace, air, pub, preprocessed=gpu_ctx.preprocess(PR.to_matrix(fixed)))
 
 
-# ------------------------------------------------------ k_reduce_prep's edges
+# ------------------------------------- k_reduce_matrix's edges inside a proof
 # The kernel that adds the preprocessed matrix's terms to the FRI input loads a
 # row in chunks of three columns (RR_CHUNK), one chunk ahead, and keeps the wp
 # alpha powers in dynamic LDS behind the 3 KiB reduction table: 36 bytes a
@@ -381,7 +381,7 @@ def _lds_per_workgroup():
 
 
 def test_refusal_boundary_of_the_prep_reduction(gpu_ctx):
-    """the widest matrix reduce_prep_fits allows proves and verifies, one
+    """the widest matrix whose alpha powers the LDS holds proves and verifies, one
     column more is LSP_E_ARG and leaves the context usable"""
     from linea_stark_prover_amd import _lib as L
     from linea_stark_prover_amd import prover as P

@@ -157,6 +157,19 @@ def _handle(L, data):
 @pytest.mark.parametrize("layout", ["a", "b"])
 @pytest.mark.parametrize("name,h", SHAPES)
 def test_deserialize_serialize_is_the_identity_and_the_views_are_the_references_parse(env, proofs, name, h, layout):
+    _round_trip_and_views(env, proofs, name, h, layout)
+
+
+@pytest.mark.parametrize("layout", ["a", "b"])
+def test_the_list_codec_at_h_8(env, proofs, layout):
+    """h = 8 (none of SHAPES): an LSPPRF03 proof goes through lsp_proof_deserialize
+    and lsp_proof_serialize byte for byte with both views the reference's own
+    parse; the LSPPRF02 proof answers LSP_E_STATE to the preprocessed view"""
+    assert proofs("keys3", 8, layout)[0][:8] == (b"LSPPRF03" if layout == "b" else b"LSPPRF02")
+    _round_trip_and_views(env, proofs, "keys3", 8, layout)
+
+
+def _round_trip_and_views(env, proofs, name, h, layout):
     from linea_stark_prover_amd.field import from_mont
     from linea_stark_prover_amd.proof import Proof, preprocessed_openings
     from linea_stark_prover_amd.prover import _take_proof
