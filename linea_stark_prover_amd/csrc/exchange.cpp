@@ -78,14 +78,13 @@ double calibrate_intt(lsp_ctx* ctx, uint32_t log_h, size_t w, int reps, const st
     Fr* y = ctx->fbuf("calib_intt_y", h * w);
     // h x w values (the raw-column generator: column-major, read here as rows)
     LSP_HIP(launch_gen_raw_perm(0x43414c4942ull /* "CALIB" */, h, (uint32_t)w, 1, 0, x, y, ctx->stream));
-    const uint4* tw = ctx->twiddle29(log_h, true);
     // device time between events around a burst of 8 back-to-back inverses
     // (what a proof's phase timer sees of a GPU that is busy): host wall time
     // adds launch and synchronisation latency, and one inverse after an idle
     // gap runs at a clock still ramping up -- 10-13 % slower than the proofs'
     // own phase at 2^20 x 4 (tests/test_gpu_calibration.py)
     constexpr int burst = 8;
-    auto inv = [&] { LSP_HIP(launch_intt(x, ColMap::plain((uint32_t)w), y, w, log_h, tw, ctx->stream)); };
+    auto inv = [&] { intt_device(ctx, x, ColMap::plain((uint32_t)w), y, w, log_h); };
     StreamTimer timer;
     std::vector<double> t;
     for (int r = 0; r <= reps; ++r) {

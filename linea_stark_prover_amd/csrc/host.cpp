@@ -436,7 +436,6 @@ lsp_ctx::~lsp_ctx() {
         if (kv.second.p) (void)hipFree(kv.second.p);
     for (auto& kv : hpool)
         if (kv.second.p) (void)hipHostFree(kv.second.p);
-    for (auto& kv : twiddles) (void)hipFree(kv.second);
     for (auto& kv : stage_ev) (void)hipEventDestroy(kv.second);
     for (hipEvent_t e : event_pool) (void)hipEventDestroy(e);
     for (auto& t : pending_timings) {
@@ -568,29 +567,16 @@ unsigned lsp::default_host_threads() {
     return n;
 }
 
-const uint4* lsp_ctx::twiddle29(uint32_t logH, bool inverse) {
-    using namespace lsp;
-    auto key = std::make_pair(logH, inverse ? 1 : 0);
-    auto it = twiddles.find(key);
-    if (it != twiddles.end()) return it->second;
-    const size_t half = logH ? (size_t(1) << (logH - 1)) : 1;
-    Fr w = host_two_adic_generator(logH);
-    if (inverse) w = fr_inv(w);
-    const uint32_t lg = logH ? logH - 1 : 0;
-    const uint32_t L1 = (lg + 1) / 2, L2 = lg - L1;
-    Fr* tab = fbuf("tw_tab_tmp", (1ull << L1) + (1ull << L2));
-    Fr* base = fbuf("tw_base_tmp", 1);
-    LSP_HIP(hipMemcpyAsync(base, &w, sizeof(Fr), hipMemcpyHostToDevice, stream));
-    LSP_HIP(launch_pow_tables(base, 1, L1, L2, nullptr, tab, stream));
-    Fr* pw = fbuf("tw_pow_tmp", half);
-    LSP_HIP(launch_powers(tab, L1, half, pw, stream));
-    uint4* out = nullptr;
-    const size_t n = logH ? (size_t(1) << logH) - 1 : 1;
-    LSP_HIP(hipMalloc(&out, n * 3 * sizeof(uint4)));
-    LSP_HIP(launch_stage_twiddles(pw, logH, out, stream));
-    LSP_HIP(hipStreamSynchronize(stream));
-    twiddles[key] = out;
-    return out;
+const lsp::Fr* lsp_ctx::table(const std::string& key, size_t n, const std::function<void(lsp::Fr*)>& fill,
+                              const char* scratch) {
+    const auto it = key.empty() ? tables.end() : tables.find(key);
+    if (it != tables.end()) return it->second;
+    const bool keep = !key.empty() && (!scratch || tables.size() < 256);
+    lsp::Fr* tab = fbuf(keep ? key : std::string(scratch), n);
+    fill(tab);
+    LSP_HIP(hipStreamSynchronize(stream));  // the fill's host temporaries may die now
+    if (keep) tables[key] = tab;
+    return tab;
 }
 
 void lsp_ctx::sync() { LSP_HIP(hipStreamSynchronize(stream)); }

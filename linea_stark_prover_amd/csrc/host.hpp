@@ -532,8 +532,18 @@ struct lsp_ctx {
     // (off, or only the named phases)
     bool phase_timing = true;
     std::vector<std::string> phase_only;
-    std::map<std::pair<uint32_t, int>, uint4*> twiddles;
-    std::map<std::string, const lsp::Fr*> ptabs;  // cached power tables (lde.cpp pow_table), pool-owned
+    // Device tables built once per key and kept while the context lives
+    // (pool-owned): power, twist and twiddle tables (lde.cpp), the quotient's
+    // inverted selector denominators (stages.cpp).
+    std::map<std::string, const lsp::Fr*> tables;
+    // The n-element table cached under `key`, built on first use: fill(tab)
+    // enqueues on the stream whatever writes it and may read host temporaries
+    // (a miss drains the stream before it returns).  With `scratch`, callers
+    // with ever new keys cannot grow the cache without bound: once 256 tables
+    // are cached -- or always, for an empty key -- the table is built in the
+    // pool buffer of that name and not kept.
+    const lsp::Fr* table(const std::string& key, size_t n, const std::function<void(lsp::Fr*)>& fill,
+                         const char* scratch = nullptr);
     // Inside lsp_prove the host-made tree-top layers are only read by the query
     // gather at the end, so their uploads wait there instead of delaying the next
     // kernel on the stream (merkle.cpp commit_device / flush_top_uploads).
@@ -569,7 +579,8 @@ struct lsp_ctx {
     // buffer `name`: the caller's memory may be reused at return and the
     // stream is not drained (only the previous copy out of `name` is awaited)
     void h2d_async(const std::string& name, void* dst, const void* src, size_t bytes);
-    // w_H^x (or its inverse) for x < H/2, in the 29-bit Montgomery form the NTT multiplies by (k_ntt.hip)
+    // stage-major powers of w_H (or of its inverse), in the 29-bit-limb slots the NTT multiplies by
+    // (launch_stage_twiddles; a cached table, lde.cpp)
     const uint4* twiddle29(uint32_t logH, bool inverse);
     lsp::HostPool& host_pool();
     void sync();

@@ -35,13 +35,11 @@
 namespace lsp {
 
 namespace {
-// PASS_INV_FWD: the inverse transform's last pass fused with the forward's first (k_ntt_rm)
-enum PassMode : int { PASS_INPLACE = 0, PASS_INV_FIRST = 1, PASS_INV_FWD = 2 };
-
+// One launch of k_ntt_rm: a planned pass (ntt_plan.hpp) and the arrays and tables it works on
 struct NttPass {
     const Fr* src;      // PASS_INV_FIRST: caller rows; PASS_INV_FWD: X after the earlier inverse passes (or caller rows)
     ColMap src_map;     // where column c of the transform sits in src (PASS_INV_FIRST, PASS_INV_FWD)
-    uint32_t no_inv;    // PASS_INV_FWD: src holds the coefficients already (no inverse stages; launch_lde_coeffs)
+    uint32_t no_inv;    // PASS_INV_FWD: src holds the coefficients already (no inverse stages; LDE_FWD)
     Fr* dst;            // the arrays being transformed (h rows each, batch of `narr` arrays, row-major w)
     const uint4* tw;    // stage-major twiddles (launch_stage_twiddles), 29-bit limbs, 3 x uint4 per element
     const uint4* tw_inv;  // PASS_INV_FWD: the inverse transform's twiddles
@@ -151,52 +149,14 @@ struct TileLds {
     }
 };
 
-// The LDS slot of tile element e: an XOR swizzle of its low bits by higher
-// bits, e ^ ((e >> 1) & 8) ^ ((e >> 2) & 31) (bits 2..6 -> 0..4, bit 4 -> 3).
-// Unswizzled, the radix-4 groups at distances 1 and 4 (and 2 and 8 with two
-// columns per row) put a wave's lanes on a quarter of the banks: 14 and 8.7
-// extra LDS cycles per instruction, 3.6 per LDS instruction over a pass, as
-// the PMC measured (SQ_LDS_BANK_CONFLICT / SQ_INSTS_LDS 3.9 / 3.1 / 2.2,
-// profiles/r05l_valu_pmc.txt).  This map makes every ds_read_b128 16-lane
-// group, ds_read/write_b32 32-lane half and ds_write_b128 8-lane group of
-// every radix-4 distance at 1 and 2 columns per row hit distinct banks (one
-// 2-way group left, the radix-2 stage at distance 1 with 2 columns), and at
-// 4 and 8 columns too (tools/lds_banks.py --swizzle ntt, found by the search
-// there; of the maps that do this, the cheapest found: two shift-mask terms,
-// half the VALU of the five-bit map tried first, which the fused pass paid
-// for: +5 % on a VALU-bound kernel).  It is XOR-linear and moves bits only downwards, so it permutes
-// [0, 2^j) for every j: the tile's size is unchanged, and a quad's members
-// e0 | m de (e0 zero at de's bits) sit at tswz(e0) ^ tswz(m de), one wave-
-// uniform XOR each.
-//
-// Measured (round 6, profiles/r06_lds_swizzle.txt): the swizzle takes the
-// passes' SQ_LDS_BANK_CONFLICT / SQ_INSTS_LDS from 3.9 / 2.2 / 3.1 to 0.2 / 0.4
-// / 0.2 and their LDS wait share from 6.6 / 2.8 / 3.6 to 3.4 / 1.4 / 2.1 per
-// LDS instruction -- and the LDE's time not at all (2^19 x 8: 3.183 against
-// 3.179 ms, medians of 8 alternating runs), while whole proofs ran 0.22-0.27
-// ms slower with it (paired, both orders): the passes are VALU-bound, the
-// conflicts were hidden behind the other waves' VALU work, and the map's
-// instructions are not.  So the tile ships unswizzled; LSP_NTT_SWZ builds it
-// (tools/variant_lib.py).
-__device__ __forceinline__ uint32_t tswz(uint32_t e) {
-#ifdef LSP_NTT_SWZ
-    return e ^ ((e >> 1) & 8u) ^ ((e >> 2) & 31u);
-#else
-    return e;
-#endif
-}
-
+// The tile's LDS slots are the element indices.  An XOR swizzle of them removes
+// the radix-4 groups' bank conflicts and no time: the passes are VALU-bound
+// (profiles/r06_lds_swizzle.txt; docs/HISTORY.md, "NTT variants measured and dropped").
 // The fused pass's twiddle cache in LDS: 48-byte slots (limbs 0-3, 4-7, 8 +
-// padding), read by f29_load48.  LSP_NTT_TWL_PLANES stores it in three planes
-// as TileLds instead (36 bytes an entry, the limb-8 words at 4-byte stride, so
-// distinct entries never share a ds_read_b32 bank within 32 of them): measured
-// 2 % slower over the whole LDE (2^19 x 8: 3.207 against 3.131 ms,
-// profiles/r06_lds_swizzle.txt), so the slots stay.
+// padding), read by f29_load48.  Three planes as TileLds were 2 % slower over
+// the whole LDE (profiles/r06_lds_swizzle.txt; docs/HISTORY.md).
 struct TwlLds {
     uint4* a;
-    uint4* b;
-    uint32_t* c;
-#ifndef LSP_NTT_TWL_PLANES  // 48-byte slots, all in `a` (the planes are the A/B variant)
     __device__ __forceinline__ F29 get(uint32_t i) const { return f29_load48(a + 3 * i); }
     __device__ __forceinline__ void put(uint32_t i, const uint4* src) const {
         a[3 * i] = src[0];
@@ -204,22 +164,6 @@ struct TwlLds {
         a[3 * i + 2] = src[2];
     }
     static constexpr size_t BYTES = 3 * sizeof(uint4);
-#else
-    __device__ __forceinline__ F29 get(uint32_t i) const {
-        const uint4 x = a[i], y = b[i];
-        F29 o;
-        o.l[0] = x.x; o.l[1] = x.y; o.l[2] = x.z; o.l[3] = x.w;
-        o.l[4] = y.x; o.l[5] = y.y; o.l[6] = y.z; o.l[7] = y.w;
-        o.l[8] = c[i];
-        return o;
-    }
-    __device__ __forceinline__ void put(uint32_t i, const uint4* src) const {
-        a[i] = src[0];
-        b[i] = src[1];
-        c[i] = src[2].x;
-    }
-    static constexpr size_t BYTES = 2 * sizeof(uint4) + sizeof(uint32_t);
-#endif
 };
 
 // Two radix-2 stages in registers (radix-4 groups): per group 4 elements are
@@ -310,8 +254,6 @@ __device__ __forceinline__ void dit4(F29& v0, F29& v1, F29& v2, F29& v3, const F
 // the coefficients are not re-read for every coset.  That pass is fused with
 // the inverse transform's last pass, which covers the same rows (stride
 // 2^(logH - k)): the coefficients never go to HBM.
-constexpr uint32_t NTT_THREADS = 256;
-constexpr uint32_t NTT_MAX_EL = 1024;  // 2^k x G x CW
 __device__ __forceinline__ uint32_t k_pos(uint32_t k) { return 1u << k; }  // positions of a tile
 
 template <int LOGCW>
@@ -338,6 +280,44 @@ struct TileGeom {
     }
 };
 
+// The columns of a workgroup's chunk: c0 .. c0 + cw - 1 of the w in a row;
+// cw < 2^LOGCW in a last chunk, whose other tile columns are padding
+struct TileCols {
+    uint32_t c0, cw, w;
+};
+
+// The walk over a tile's elements, thread-strided: e -> (position, group,
+// column) -> row and LDS slot.  tile_load fills the tile from src(row, column
+// of the matrix) and zeroes the padding columns (the butterflies reduce them
+// too); tile_store writes the real columns to the rows of `base`.
+template <int LOGCW, class Src>
+__device__ __forceinline__ void tile_load(const TileLds& T, const TileGeom<LOGCW>& gm, const TileCols& cols, uint64_t H,
+                                          uint32_t n_el, Src&& src) {
+    for (uint32_t e = threadIdx.x; e < n_el; e += NTT_THREADS) {
+        uint32_t t, g, c;
+        gm.split(e, t, g, c);
+        if (c >= cols.cw) {
+            T.put(gm.idx(t, g, c), f29_zero());
+            continue;
+        }
+        const uint32_t row = gm.row_of(t, g);
+        if (!LSP_BOUNDS(row < H && gm.idx(t, g, c) < n_el && cols.c0 + c < cols.w)) continue;
+        T.put(gm.idx(t, g, c), src(row, cols.c0 + c));
+    }
+}
+
+template <int LOGCW>
+__device__ __forceinline__ void tile_store(const TileLds& T, const TileGeom<LOGCW>& gm, const TileCols& cols, uint64_t H,
+                                           uint32_t n_el, Fr* base, bool canon) {
+    for (uint32_t e = threadIdx.x; e < n_el; e += NTT_THREADS) {
+        uint32_t t, g, c;
+        gm.split(e, t, g, c);
+        if (c >= cols.cw) continue;
+        if (!LSP_BOUNDS(gm.row_of(t, g) < H && gm.idx(t, g, c) < n_el && cols.c0 + c < cols.w)) continue;
+        base[(size_t)gm.row_of(t, g) * cols.w + cols.c0 + c] = f29_store(T.get(gm.idx(t, g, c)), canon);
+    }
+}
+
 // The fused pass's forward twiddles, cached in LDS once per workgroup: its
 // tile rows are t 2^logL + gid (s0 = 0, logL + k = logH), so DIF stage s < k
 // reads w^(gid + (t mod 2^(k-1-s)) 2^logL) -- 2^(k-1-s) distinct values per row
@@ -358,7 +338,7 @@ __device__ __forceinline__ uint32_t twl_index(const TileGeom<LOGCW>& gm, uint32_
 template <bool DIF, int LOGCW>
 __device__ __forceinline__ void tile_stages(const TileLds& T, const TileGeom<LOGCW>& gm, const uint4* __restrict__ tw,
                                             uint32_t s0, uint32_t logH, uint32_t n_el,
-                                            TwlLds twl = TwlLds{nullptr, nullptr, nullptr},
+                                            TwlLds twl = TwlLds{nullptr},
                                             const uint4* qt = nullptr, uint32_t twl_n = 0) {
     constexpr uint32_t CW = 1u << LOGCW;
     const uint32_t k = gm.k, G = 1u << gm.logG;
@@ -395,9 +375,8 @@ __device__ __forceinline__ void tile_stages(const TileLds& T, const TileGeom<LOG
                 const uint32_t t0 = ((pp & ~bmask) << 2) | (pp & bmask);
                 const uint32_t e0 = (t0 << cshift) + (g << LOGCW) + c, de = (1u << b) << cshift;
                 if (!LSP_BOUNDS(e0 + 3 * de < n_el && t0 + 3 * (1u << b) < k_pos(k))) continue;
-                // e0 is zero at de's two bits: member m sits at tswz(e0) ^ tswz(m de)
-                const uint32_t x0 = tswz(e0), d1 = tswz(de), d2 = tswz(2 * de);
-                const uint32_t x1 = x0 ^ d1, x2 = x0 ^ d2, x3 = x1 ^ d2;
+                // e0 is zero at de's two bits: member m sits at e0 ^ m de
+                const uint32_t x0 = e0, x1 = e0 ^ de, x2 = e0 ^ (2 * de), x3 = x1 ^ (2 * de);
                 F29 v0 = T.get(x0), v1 = T.get(x1), v2 = T.get(x2), v3 = T.get(x3);
                 const uint32_t r0 = gm.row_of(t0, g), dr = (1u << b) << gm.logL;
                 if constexpr (DIF) {
@@ -435,7 +414,7 @@ __device__ __forceinline__ void tile_stages(const TileLds& T, const TileGeom<LOG
             const uint32_t t0 = ((pp >> logd) << (logd + 1)) | (pp & dmask);
             const uint32_t e0 = (t0 << cshift) + (g << LOGCW) + c, e1 = e0 + ((1u << logd) << cshift);
             if (!LSP_BOUNDS(e1 < n_el)) continue;
-            const uint32_t a0 = tswz(e0), a1 = a0 ^ tswz((1u << logd) << cshift);  // e0 zero at that bit
+            const uint32_t a0 = e0, a1 = e0 ^ ((1u << logd) << cshift);  // e0 zero at that bit
             const F29 a = T.get(a0), b = T.get(a1);
             if (trivial) {
                 T.put(a0, red(f29_lazy2(a, b), qt));
@@ -480,6 +459,7 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_rm(NttPass p) {
     const uint32_t tile = rem / p.nchunk;
     const uint32_t c0 = (rem - tile * p.nchunk) << LOGCW;
     const uint32_t cw = min(CW, p.w - c0);
+    const TileCols cols{c0, cw, p.w};
     const uint32_t n_el = (K << logG) << LOGCW;
     const TileGeom<LOGCW> gm{p.k, logG, p.logL, tile << logG};
     const TileLds T{lds_raw, lds_raw + n_el, reinterpret_cast<uint32_t*>(lds_raw + 2 * n_el)};
@@ -487,25 +467,24 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_rm(NttPass p) {
     // LDS already limits it to 2 workgroups per CU); published by the barrier
     // after the tile's load below
     const uint4* qt = nullptr;
-#ifndef LSP_NTT_NO_QT  // A/B switch (tools/variant_lib.py): f29_reduce everywhere
     if constexpr (!FWD_FIRST) {
         uint4* q = reinterpret_cast<uint4*>(T.c + n_el);
         f29_qtab_init(q);
         qt = q;
     }
-#endif
     constexpr uint32_t NREG = FWD_FIRST ? NTT_MAX_EL / NTT_THREADS : 1;
+    // the fused pass: this thread's coefficients and their LDS slots, for every coset
     F29 xr[NREG];
-    uint32_t xs[NREG];  // the fused pass: the LDS slots of this thread's elements, for every coset
+    uint32_t xs[NREG];
     // the forward twiddles of this tile in LDS (after the tile and the per-row
     // twist factors; published by the barrier after the coefficient load below)
     // (by value: a pointer to it would put the struct in scratch memory)
-    TwlLds twl{nullptr, nullptr, nullptr};
+    TwlLds twl{nullptr};
     if (FWD_FIRST && p.twl_n) {
         const bool rt = !p.twist_per_col || p.ratio;  // the row factors sit between the tile and these
         const size_t off = (size_t)n_el * sizeof(F29) + (rt ? (size_t)(K << logG) * sizeof(F29) : 0);
         uint4* base = reinterpret_cast<uint4*>(reinterpret_cast<char*>(lds_raw) + ((off + 15) & ~(size_t)15));
-        twl = TwlLds{base, base + p.twl_n, reinterpret_cast<uint32_t*>(base + 2 * p.twl_n)};
+        twl = TwlLds{base};
         const uint32_t per = K - 1;  // entries per row group
         for (uint32_t e = threadIdx.x; e < p.twl_n; e += NTT_THREADS) {
             const uint32_t g = e / per, r = e - g * per;
@@ -519,24 +498,18 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_rm(NttPass p) {
             twl.put(e, p.tw + 3 * gi);
         }
     }
+    // a source element through the pass's column map (a padding column reads as zero)
+    auto gathered = [&](uint32_t srow, uint32_t col) -> F29 {
+        size_t si;
+        return src_at(p.src_map, H, srow, col, si) ? f29_repack_in(p.src[si]) : f29_zero();
+    };
     if (FWD_FIRST) {
         // ---- the inverse transform's last stages over these rows (logH - k ..
         // logH - 1; from the caller's rows, gathered bit-reversed, when the
         // inverse has only this pass), then the coefficients (x h) stay in registers
-        for (uint32_t e = threadIdx.x; e < n_el; e += NTT_THREADS) {
-            uint32_t t, g, c;
-            gm.split(e, t, g, c);
-            if (c >= cw) {  // padding columns of the last chunk: zeros (the butterflies reduce them too)
-                T.put(tswz(gm.idx(t, g, c)), f29_zero());
-                continue;
-            }
-            const uint32_t row = gm.row_of(t, g);
-            const uint32_t srow = p.inv_gather ? brev_bits(row, p.logH) : row;
-            size_t si;
-            if (!LSP_BOUNDS(row < H && gm.idx(t, g, c) < n_el && c0 + c < p.w)) continue;
-            T.put(tswz(gm.idx(t, g, c)),
-                  src_at(p.src_map, H, srow, c0 + c, si) ? f29_repack_in(p.src[si]) : f29_zero());
-        }
+        tile_load(T, gm, cols, H, n_el, [&](uint32_t row, uint32_t col) {
+            return gathered(p.inv_gather ? brev_bits(row, p.logH) : row, col);
+        });
         __syncthreads();
         if (!p.no_inv) tile_stages<false, LOGCW>(T, gm, p.tw_inv, p.logH - p.k, p.logH, n_el);
 #pragma unroll
@@ -544,7 +517,7 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_rm(NttPass p) {
             const uint32_t e = threadIdx.x + j * NTT_THREADS;
             uint32_t t, g, c;
             gm.split(e, t, g, c);
-            xs[j] = tswz(gm.idx(t, g, c));
+            xs[j] = gm.idx(t, g, c);
             if (e < n_el && c < cw) xr[j] = T.get(xs[j]);  // normalised, < 8.3 r
         }
     }
@@ -573,7 +546,11 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_rm(NttPass p) {
             }
             __syncthreads();
         }
-        // ---- load (twisting the registers, or from the array)
+        // ---- load: the registers times the twist, or from the array.  The fused
+        // pass's twist and its store below stay loops of their own, unrolled over
+        // this thread's NREG register-resident elements (xr, xs): through
+        // tile_store the 2^19 x 14 LDE measured 1.5-2 % slower
+        // (profiles/lde_refactor_bench.txt)
         if (FWD_FIRST) {
 #pragma unroll
             for (uint32_t jr = 0; jr < NREG; ++jr) {
@@ -600,30 +577,17 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_rm(NttPass p) {
                     T.put(xs[jr], f29_mul(xr[jr], f));  // < 8.3 r
                 }
             }
+        } else if (MODE == PASS_INV_FIRST) {
+            tile_load(T, gm, cols, H, n_el,
+                      [&](uint32_t row, uint32_t col) { return gathered(brev_bits(row, p.logH), col); });
         } else {
-            for (uint32_t e = threadIdx.x; e < n_el; e += NTT_THREADS) {
-                uint32_t t, g, c;
-                gm.split(e, t, g, c);
-                if (c >= cw) {  // padding columns of the last chunk: zeros (the butterflies reduce them too)
-                    T.put(tswz(gm.idx(t, g, c)), f29_zero());
-                    continue;
-                }
-                const uint32_t row = gm.row_of(t, g);
-                if (!LSP_BOUNDS(row < H && gm.idx(t, g, c) < n_el && c0 + c < p.w)) continue;
-                F29 v;
-                size_t si;
-                if (MODE == PASS_INV_FIRST)
-                    v = src_at(p.src_map, H, brev_bits(row, p.logH), c0 + c, si) ? f29_repack_in(p.src[si]) : f29_zero();
-                else
-                    v = f29_repack_in(base[(size_t)row * p.w + c0 + c]);
-                T.put(tswz(gm.idx(t, g, c)), v);
-            }
+            tile_load(T, gm, cols, H, n_el,
+                      [&](uint32_t row, uint32_t col) { return f29_repack_in(base[(size_t)row * p.w + col]); });
         }
         __syncthreads();
         tile_stages<DIF, LOGCW>(T, gm, p.tw, p.s0, p.logH, n_el, twl, qt, FWD_FIRST ? p.twl_n : 0u);
-        // ---- store
         const bool canon = p.canon != 0;
-        if constexpr (FWD_FIRST) {  // this thread's elements, at the slots computed once (xs)
+        if constexpr (FWD_FIRST) {
 #pragma unroll
             for (uint32_t jr = 0; jr < NREG; ++jr) {
                 const uint32_t e = threadIdx.x + jr * NTT_THREADS;
@@ -634,13 +598,7 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_rm(NttPass p) {
                 base[(size_t)gm.row_of(t, g) * p.w + c0 + c] = f29_store(T.get(xs[jr]), canon);
             }
         } else {
-            for (uint32_t e = threadIdx.x; e < n_el; e += NTT_THREADS) {
-                uint32_t t, g, c;
-                gm.split(e, t, g, c);
-                if (c >= cw) continue;
-                if (!LSP_BOUNDS(gm.row_of(t, g) < H && gm.idx(t, g, c) < n_el && c0 + c < p.w)) continue;
-                base[(size_t)gm.row_of(t, g) * p.w + c0 + c] = f29_store(T.get(tswz(gm.idx(t, g, c))), canon);
-            }
+            tile_store(T, gm, cols, H, n_el, base, canon);
         }
     }
 }
@@ -667,7 +625,7 @@ __global__ __launch_bounds__(256) void k_fold_subcoset(const Fr* __restrict__ co
 
 // out[i][c] = X[i][c] f^i canonical, f^i from a two-level table of 29-bit-form
 // factors (pow2l29): the coefficients of an inverse transform (h * c_i, as
-// launch_intt leaves them) times (1/h) shift^-i (coset_idft_batch)
+// LDE_INV leaves them) times (1/h) shift^-i (coset_idft_batch)
 __global__ __launch_bounds__(256) void k_scale_coeffs(const Fr* __restrict__ X, size_t h, uint32_t w,
                                                       const Fr* __restrict__ tab, uint32_t L1, Fr* __restrict__ out) {
     const size_t e = gtid();
@@ -727,182 +685,91 @@ __global__ __launch_bounds__(256) void k_powers(const Fr* __restrict__ tab, uint
     if (i < n) out[i] = pow2l(tab, L1, i);
 }
 
-void plan_passes(uint32_t logH, uint32_t kmax, uint32_t* ks, uint32_t& np) {
-    np = 0;
-    if (logH <= kmax) {
-        ks[np++] = logH;
-        return;
-    }
-    const uint32_t P = (logH + kmax - 1) / kmax;
-    for (uint32_t q = 0; q < P; ++q) ks[np++] = logH / P + (q < logH % P ? 1 : 0);
+// the LDS parts the plan sizes are the ones k_ntt_rm carves out
+static_assert(sizeof(F29) == NTT_EL_BYTES && TwlLds::BYTES == NTT_TWL_BYTES &&
+              F29_QTAB_N * 3 * sizeof(uint4) == NTT_QTAB_BYTES);
+
+// the kernel of a planned pass at its column chunk
+using NttKernel = void (*)(NttPass);
+template <bool DIF, int MODE>
+NttKernel ntt_kernel_cw(uint32_t logCW) {
+    static constexpr NttKernel byCW[4] = {k_ntt_rm<DIF, MODE, 0>, k_ntt_rm<DIF, MODE, 1>, k_ntt_rm<DIF, MODE, 2>,
+                                          k_ntt_rm<DIF, MODE, 3>};
+    return byCW[std::min(logCW, 3u)];
+}
+NttKernel ntt_kernel(const PlannedPass& pp) {
+    if (pp.mode == PASS_INV_FWD) return ntt_kernel_cw<true, PASS_INV_FWD>(pp.logCW);
+    if (pp.dif) return ntt_kernel_cw<true, PASS_INPLACE>(pp.logCW);
+    return pp.mode == PASS_INV_FIRST ? ntt_kernel_cw<false, PASS_INV_FIRST>(pp.logCW)
+                                     : ntt_kernel_cw<false, PASS_INPLACE>(pp.logCW);
+}
+
+// LSP_NTT_KMAX / LSP_NTT_LOGCW / LSP_NTT_TWL, read once per process
+const NttKnobs& ntt_knobs() {
+    static const NttKnobs kn = [] {
+        NttKnobs k;
+        if (const char* e = std::getenv("LSP_NTT_KMAX")) k.kmax = (uint32_t)std::min(10, std::max(1, std::atoi(e)));
+        if (const char* e = std::getenv("LSP_NTT_LOGCW")) k.logcw = std::min(3, std::max(0, std::atoi(e)));
+        if (const char* e = std::getenv("LSP_NTT_TWL")) k.twl = *e != '0';
+        return k;
+    }();
+    return kn;
 }
 }  // namespace
 
-// the passes of an LDE (WHAT = LDE_FULL), of its inverse half only
-// (LDE_INV: X <- h * coefficients) or of its forward half only (LDE_FWD: from
-// h * coefficients at `in` through `map`)
-enum LdeWhat { LDE_FULL = 0, LDE_INV = 1, LDE_FWD = 2 };
-
-static hipError_t run_lde(LdeWhat what, const Fr* in, ColMap map, Fr* X, Fr* out, size_t w, uint32_t logh,
-                          uint32_t ncosets, const uint4* tw_inv, const uint4* tw_fwd, const Fr* twist, uint32_t L1,
-                          uint32_t L2, int twist_per_col, const Fr* ratio, hipStream_t st) {
-    if (w == 0) return hipSuccess;
+hipError_t launch_ntt(const NttLaunch& a, hipStream_t st) {
+    if (a.w == 0) return hipSuccess;
+    const uint32_t nb = a.what == LDE_INV ? 1u : a.ncosets;
     uint32_t log_narr = 0;
-    while ((1u << log_narr) < ncosets) ++log_narr;
-    if (ratio && (ncosets < 2 || (1u << log_narr) != ncosets)) return hipErrorInvalidValue;
-    // Tile = 2^k positions x G groups x CW columns = 1024 elements (36 KiB of
-    // LDS) where the array allows it, so every radix-4 group gives each of the
-    // 256 threads one quad.  Up to k = 10 stages per pass with one column per
-    // tile (2^19 points in 2 passes instead of 3: fewer HBM round trips); a
-    // pass with fewer stages takes the widest column chunk that still fits
-    // (k = 9: CW = 2, ..., k <= 7: CW = 8), and the narrow row accesses are
-    // merged in L2 by the XCD-aware tile order.  LSP_NTT_LOGCW (minimum column
-    // chunk) / LSP_NTT_KMAX override (LOGCW=3 KMAX=7: the r01 shape).
-    // minimum log2 column chunk (bounds k).  Narrow chunks rely on the XCD's L2
-    // holding a tile's rows until all its chunks have read them; from ~48
-    // columns (1.5 MiB per 1024-row tile) that stops working, and passes of
-    // whole 256-byte row segments win: 2^20 x 184 172.6 -> 161.5 ms, 2^19 x 64
-    // 27.8 -> 27.4 ms; at 8..32 columns the 2-pass plan stays ahead (2^19 x 14
-    // 6.0 against 7.0 ms) -- tools/sweep_lde_logcw.sh, profiles/r02u_lde_logcw.txt
-    static const int logcw_env = [] {
-        const char* e = std::getenv("LSP_NTT_LOGCW");
-        return e ? std::min(3, std::max(0, std::atoi(e))) : -1;
-    }();
-    static const bool twl_env = [] {  // LSP_NTT_TWL=0: the fused pass reads its twiddles from HBM
-        const char* e = std::getenv("LSP_NTT_TWL");
-        return !(e && *e == '0');
-    }();
-    static const uint32_t kmax_env = [] {
-        const char* e = std::getenv("LSP_NTT_KMAX");
-        return e ? (uint32_t)std::min(10, std::max(1, std::atoi(e))) : 10u;
-    }();
-    uint32_t logCWmax = 0;  // the power of two >= min(w, 8)
-    while ((1u << logCWmax) < w && logCWmax < 3) ++logCWmax;
-    const uint32_t logcw_min = logcw_env >= 0 ? (uint32_t)logcw_env : (w >= 48 ? 1u : 0u);
-    const uint32_t kmax = std::min(kmax_env, 10 - std::min(logCWmax, logcw_min));
-    uint32_t ks[16], np;
-    plan_passes(logh, kmax, ks, np);
-    // inverse: passes ks[0], ..., ks[np-1] (DIT, stages in increasing order);
-    // forward: ks[np-1], ..., ks[0] (DIF), so the forward's first pass covers
-    // the rows of the inverse's last pass and the two run as one (PASS_INV_FWD)
-    auto launch = [&](bool dif, int mode, uint32_t k, uint32_t s0, uint32_t narr, const Fr* src, Fr* dst,
-                      const uint4* tw, bool canon) -> hipError_t {
-        // widest column chunk the 1024-element tile allows at this k (CW = 1 at k = 10)
-        const uint32_t logCW = std::min(logCWmax, 10 - k);
-        const uint32_t CW = 1u << logCW;
-        const uint32_t nchunk = (uint32_t)((w + CW - 1) / CW);
-        const uint32_t want = k + logCW >= 10 ? 0u : 10 - k - logCW;
-        const uint32_t logG = std::min(logh - k, want);
-        NttPass p;
-        p.src = src;
-        p.src_map = map;  // read only by the passes with a `src` (PASS_INV_FIRST / PASS_INV_FWD)
-        p.no_inv = what == LDE_FWD ? 1u : 0u;
-        p.dst = dst;
-        p.tw = tw;
-        p.tw_inv = tw_inv;
-        p.inv_gather = (np == 1 && what == LDE_FULL) ? 1u : 0u;
-        p.twist = twist;
-        p.L1 = L1;
-        p.L2 = L2;
-        p.twist_per_col = (uint32_t)twist_per_col;
-        p.logH = logh;
-        p.s0 = s0;
-        p.k = k;
-        p.logL = dif ? (logh - s0 - k) : s0;
-        p.logG = logG;
-        p.w = (uint32_t)w;
-        p.nchunk = nchunk;
-        p.canon = canon ? 1u : 0u;
-        p.narr = narr;
-        p.ratio = mode == PASS_INV_FWD ? ratio : nullptr;
-        p.log_narr = log_narr;
-        // the fused pass loops over the cosets inside each workgroup
-        const uint64_t tiles = (uint64_t)(mode == PASS_INV_FWD ? 1 : narr) * ((1ull << logh) >> (k + logG)) * nchunk;
-        // tile, plus one twist (or chain ratio) factor per row in the fused pass
-        const bool fac = mode == PASS_INV_FWD && (!twist_per_col || ratio);
-        size_t lds = ((size_t(1) << (k + logG)) * CW + (fac ? (size_t(1) << (k + logG)) : 0)) * sizeof(F29);
-        // ... and its forward twiddles when they fit (<= 512 entries, 18 KiB in planes: 2 workgroups per CU)
-        const size_t twl_n = (size_t(1) << logG) * ((size_t(1) << k) - 1);
-        p.twl_n = (mode == PASS_INV_FWD && twl_n <= 512 && twl_env) ? (uint32_t)twl_n : 0u;
-        if (p.twl_n) lds = ((lds + 15) & ~(size_t)15) + (size_t)p.twl_n * TwlLds::BYTES;
-        if (mode != PASS_INV_FWD) lds += (size_t)F29_QTAB_N * 3 * sizeof(uint4);  // k_ntt_rm's reduction table
-        p.xcd = (tiles / nchunk) % 8 == 0 ? 1u : 0u;
-        const dim3 grid((unsigned)tiles), blk(256);
-#define LSP_NTT_LAUNCH(DIFV, MODEV)                                                                   \
-    switch (logCW) {                                                                                  \
-        case 0: hipLaunchKernelGGL((k_ntt_rm<DIFV, MODEV, 0>), grid, blk, lds, st, p); break;         \
-        case 1: hipLaunchKernelGGL((k_ntt_rm<DIFV, MODEV, 1>), grid, blk, lds, st, p); break;         \
-        case 2: hipLaunchKernelGGL((k_ntt_rm<DIFV, MODEV, 2>), grid, blk, lds, st, p); break;         \
-        default: hipLaunchKernelGGL((k_ntt_rm<DIFV, MODEV, 3>), grid, blk, lds, st, p); break;        \
-    }
-        if (mode == PASS_INV_FWD) {
-            LSP_NTT_LAUNCH(true, PASS_INV_FWD)
-        } else if (dif) {
-            LSP_NTT_LAUNCH(true, PASS_INPLACE)
-        } else if (mode == PASS_INV_FIRST) {
-            LSP_NTT_LAUNCH(false, PASS_INV_FIRST)
-        } else {
-            LSP_NTT_LAUNCH(false, PASS_INPLACE)
-        }
-#undef LSP_NTT_LAUNCH
-        return hipGetLastError();
-    };
-    if (logh == 0) {
-        // h = 1: the coefficient is the value; every coset row equals it
-        if (what == LDE_INV || map.logb != COLMAP_PLAIN || map.c0 != 0 || map.cstep != 1 || map.stride != w)
-            return hipErrorInvalidValue;  // (the sharded prover's maps never meet h = 1)
-        for (uint32_t k = 0; k < ncosets; ++k) {
-            hipError_t e = hipMemcpyAsync(out + (size_t)k * w, in, w * sizeof(Fr), hipMemcpyDeviceToDevice, st);
+    while ((1u << log_narr) < nb) ++log_narr;
+    if (a.ratio && (nb < 2 || (1u << log_narr) != nb)) return hipErrorInvalidValue;
+    if (a.logh == 0) {
+        // h = 1: the value is the coefficient, and every coset block's row equals it
+        // (the sharded prover's maps never meet h = 1)
+        const ColMap& m = a.map;
+        if (m.logb != COLMAP_PLAIN || m.c0 != 0 || m.cstep != 1 || m.stride != a.w) return hipErrorInvalidValue;
+        for (uint32_t k = 0; k < nb; ++k) {
+            Fr* dst = a.what == LDE_INV ? a.scratch : a.out + (size_t)k * a.w;
+            if (dst == a.src) continue;
+            hipError_t e = hipMemcpyAsync(dst, a.src, a.w * sizeof(Fr), hipMemcpyDeviceToDevice, st);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
     }
-    hipError_t e = hipSuccess;
-    if (what == LDE_INV) {  // every inverse pass, the last one too, into X
-        uint32_t s0 = 0;
-        for (uint32_t q = 0; q < np && e == hipSuccess; ++q) {
-            e = launch(false, q == 0 ? PASS_INV_FIRST : PASS_INPLACE, ks[q], s0, 1, in, X, tw_inv, false);
-            s0 += ks[q];
-        }
-        return e;
-    }
-    uint32_t s0 = 0;
-    if (what == LDE_FULL)
-        for (uint32_t q = 0; q + 1 < np; ++q) {  // inverse passes before the last
-            e = launch(false, q == 0 ? PASS_INV_FIRST : PASS_INPLACE, ks[q], s0, 1, in, X, tw_inv, false);
-            if (e != hipSuccess) return e;
-            s0 += ks[q];
-        }
-    // the inverse's last stages (LDE_FULL) + the forward's first ks[np-1] stages, per coset
-    e = launch(true, PASS_INV_FWD, ks[np - 1], 0, ncosets, (np == 1 || what == LDE_FWD) ? in : X, out, tw_fwd,
-               np == 1);
-    if (e != hipSuccess) return e;
-    s0 = ks[np - 1];
-    for (uint32_t q = 1; q < np; ++q) {  // the remaining forward passes
-        const uint32_t k = ks[np - 1 - q];
-        e = launch(true, PASS_INPLACE, k, s0, ncosets, out, out, tw_fwd, q + 1 == np);
-        if (e != hipSuccess) return e;
-        s0 += k;
+    const bool row_factors = !a.twist_per_col || a.ratio;
+    for (const PlannedPass& pp : plan_ntt(a.what, a.logh, a.w, nb, row_factors, ntt_knobs())) {
+        if (pp.grid > 0x7fffffffull) return hipErrorInvalidValue;
+        const bool fused = pp.mode == PASS_INV_FWD;
+        const NttPass p{
+            .src = pp.from_src ? a.src : a.scratch,
+            .src_map = a.map,
+            .no_inv = pp.no_inv,
+            .dst = pp.dif ? a.out : a.scratch,
+            .tw = pp.dif ? a.tw_fwd : a.tw_inv,
+            .tw_inv = a.tw_inv,
+            .inv_gather = pp.inv_gather,
+            .twist = a.twist,
+            .L1 = a.L1,
+            .L2 = a.L2,
+            .twist_per_col = (uint32_t)a.twist_per_col,
+            .logH = a.logh,
+            .s0 = pp.s0,
+            .k = pp.k,
+            .logL = pp.logL,
+            .logG = pp.logG,
+            .w = (uint32_t)a.w,
+            .nchunk = pp.nchunk,
+            .canon = pp.canon,
+            .xcd = pp.xcd,
+            .twl_n = pp.twl_n,
+            .narr = pp.dif ? nb : 1u,
+            .ratio = fused ? a.ratio : nullptr,
+            .log_narr = log_narr,
+        };
+        hipLaunchKernelGGL(ntt_kernel(pp), dim3((unsigned)pp.grid), dim3(NTT_THREADS), pp.lds, st, p);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     return hipSuccess;
-}
-
-hipError_t launch_lde(const Fr* in, Fr* X, Fr* out, size_t w, uint32_t logh, uint32_t ncosets, const uint4* tw_inv,
-                      const uint4* tw_fwd, const Fr* twist, uint32_t L1, uint32_t L2, int twist_per_col,
-                      const Fr* ratio, hipStream_t st) {
-    return run_lde(LDE_FULL, in, ColMap::plain((uint32_t)w), X, out, w, logh, ncosets, tw_inv, tw_fwd, twist, L1, L2,
-                   twist_per_col, ratio, st);
-}
-
-hipError_t launch_intt(const Fr* in, ColMap map, Fr* X, size_t w, uint32_t logh, const uint4* tw_inv, hipStream_t st) {
-    return run_lde(LDE_INV, in, map, X, nullptr, w, logh, 0, tw_inv, nullptr, nullptr, 0, 0, 0, nullptr, st);
-}
-
-hipError_t launch_lde_coeffs(const Fr* coef, ColMap map, Fr* out, size_t w, uint32_t logh, uint32_t ncosets,
-                             const uint4* tw_fwd, const Fr* twist, uint32_t L1, uint32_t L2, int twist_per_col,
-                             const Fr* ratio, hipStream_t st) {
-    return run_lde(LDE_FWD, coef, map, nullptr, out, w, logh, ncosets, nullptr, tw_fwd, twist, L1, L2, twist_per_col,
-                   ratio, st);
 }
 
 hipError_t launch_fold_subcoset(const Fr* coef, ColMap map, size_t h, size_t S, uint32_t w, const Fr* fac, Fr* out,

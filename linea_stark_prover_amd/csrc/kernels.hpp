@@ -7,6 +7,7 @@
 
 #include "fr.hpp"
 #include "fr29.hpp"
+#include "ntt_plan.hpp"
 #include "poseidon2.hpp"
 
 namespace lsp {
@@ -37,33 +38,44 @@ struct ColMap {
         return m;
     }
 };
-// Coset evaluations of the h x w row-major matrix `in`: `ncosets` blocks of h
-// rows (block k on the coset of twist table k), each in bit-reversed order,
-// into row-major `out` (canonical), via X (h x w scratch, left holding
-// h * coefficients reduced below 2r).  tw_inv / tw_fwd: w_h^-x / w_h^x, x < h/2;
-// twist: two-level tables (L1, L2) of base s and scale 1/h, one per coset
+// One transform of 2^logh rows x w columns, by the passes ntt_plan.hpp plans:
+//   LDE_FULL  coset evaluations of the row-major matrix `src` (read through
+//             `map`): `ncosets` blocks of h rows (block k on the coset of twist
+//             table k), each in bit-reversed order, into row-major `out`
+//             (canonical), via `scratch` (h x w, left holding h * coefficients
+//             reduced below 2r)
+//   LDE_INV   the inverse half: scratch <- h * coefficients, natural order, of
+//             the w columns `map` picks in `src` (values on H_h); a sharded
+//             proof's ranks split it by columns
+//   LDE_FWD   the forward half: the blocks of LDE_FULL from h * coefficients at
+//             `src` through `map` (no inverse stages, no scratch)
+// logh = 0: the row goes to the scratch or to every block as it is (plain maps only).
+// tw_inv / tw_fwd: w_h^-x / w_h^x, x < h/2 (launch_stage_twiddles); twist:
+// two-level tables (L1, L2) of base s and scale 1/h, one per coset
 // (twist_per_col = 0) or per (coset, column) at index k*w + c -- all tables in
 // the 29-bit Montgomery form (launch_to_f29form; k_ntt.hip).  ratio (nullptr:
 // off; ncosets a power of two >= 2): the two-level table (L1, L2) of rho^i when
 // the shifts of blocks bitrev(0), bitrev(1), ... are s, s rho, s rho^2, ...; the
 // fused pass then uses only block 0's twist tables and chains the rest.
-hipError_t launch_lde(const Fr* in, Fr* X, Fr* out, size_t w, uint32_t logh, uint32_t ncosets, const uint4* tw_inv,
-                      const uint4* tw_fwd, const Fr* twist, uint32_t L1, uint32_t L2, int twist_per_col,
-                      const Fr* ratio, hipStream_t st);
-// The two halves of launch_lde, for a sharded proof whose ranks split the
-// inverse transform by columns (prove.cpp prove_shard):
-//   launch_intt       X (h x w) <- h * coefficients, natural order, of the w
-//                     columns `map` picks in `in` (values on H_h)
-//   launch_lde_coeffs the coset blocks of launch_lde from h * coefficients at
-//                     `coef` through `map` (no inverse stages)
-hipError_t launch_intt(const Fr* in, ColMap map, Fr* X, size_t w, uint32_t logh, const uint4* tw_inv, hipStream_t st);
-hipError_t launch_lde_coeffs(const Fr* coef, ColMap map, Fr* out, size_t w, uint32_t logh, uint32_t ncosets,
-                             const uint4* tw_fwd, const Fr* twist, uint32_t L1, uint32_t L2, int twist_per_col,
-                             const Fr* ratio, hipStream_t st);
+struct NttLaunch {
+    LdeWhat what = LDE_FULL;
+    const Fr* src = nullptr;
+    ColMap map;
+    Fr* scratch = nullptr;
+    Fr* out = nullptr;
+    size_t w = 0;
+    uint32_t logh = 0, ncosets = 0;
+    const uint4 *tw_inv = nullptr, *tw_fwd = nullptr;
+    const Fr* twist = nullptr;
+    uint32_t L1 = 0, L2 = 0;
+    int twist_per_col = 0;
+    const Fr* ratio = nullptr;
+};
+hipError_t launch_ntt(const NttLaunch& a, hipStream_t st);
 // A sub-coset of the LDE (a sharded proof over more ranks than cosets):
 // out (S x w, row-major) = the h coefficients of every column folded to S,
 // out[i][c] = sum_t coef[i + t S][c] fac[c f + t] for t < f = h / S (coef read
-// through `map`, values as launch_intt leaves them; fac: the f factors
+// through `map`, values as LDE_INV leaves them; fac: the f factors
 // sigma_c^t / f of each column in the 29-bit form, launch_to_f29form).  The
 // size-S coset NTT of the folded column equals the degree < h polynomial on
 // that size-S coset when sigma_c = (its shift)^S.

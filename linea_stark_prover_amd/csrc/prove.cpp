@@ -346,26 +346,32 @@ struct Prover {
             m.c0 = (uint32_t)host_bitrev(s.g, s.b);
             m.cstep = s.G;
             T.begin("trace inverse NTT");  // this rank's cg columns (tests/test_gpu_calibration.py)
-            LSP_HIP(launch_intt(d_trace, m, xl, cg, s.log_h, ctx->twiddle29(s.log_h, true), st));
+            intt_device(ctx, d_trace, m, xl, cg, s.log_h);
             T.end("trace inverse NTT");
             comm.allgather(ctx, xl, coef, h * cg * sizeof(Fr), "trace coefficients");
             tcoef = coef;
             tmap = ColMap::blocked(s.b, cg);
         } else if (s.sub) {  // every rank inverts every column (LSP_SHARD_SPLIT_INTT=0)
             Fr* coef = ctx->fbuf("t_coef", h * w);
-            LSP_HIP(launch_intt(d_trace, ColMap::plain((uint32_t)w), coef, w, s.log_h, ctx->twiddle29(s.log_h, true),
-                                st));
+            intt_device(ctx, d_trace, ColMap::plain((uint32_t)w), coef, w, s.log_h);
             tcoef = coef;
             tmap = ColMap::plain((uint32_t)w);
         }
-        if (s.sub)
-            subcoset_lde(ctx, tcoef, tmap, h, w, s.logN, s.b, s.g, shifts.data(), lde, "t_sub");
-        else if (s.split)
-            lde_coeffs_device(ctx, tcoef, tmap, h, w, s.lb, shifts.data(), lde, s.k0, s.nk);
-        else
-            lde_device(ctx, d_trace, h, w, s.lb, shifts.data(), lde, s.k0, s.nk);
+        rank_lde(d_trace, tcoef, tmap, w, lde, "t_sub");
         t_lde_issued = host_clock::now();
         T.end("coset_lde_batch");
+    }
+
+    // This rank's rows of one committed matrix's LDE (shifts set by the caller):
+    // a sub-coset folded from the coefficients when the proof has more ranks
+    // than cosets, else its coset blocks -- from h * coefficients at `coef`
+    // through `cmap` where the ranks split the inverse, from the local
+    // evaluations otherwise (coef null)
+    void rank_lde(const Fr* evals, const Fr* coef, ColMap cmap, size_t w, Fr* out, const char* sub_tag) {
+        if (s.sub) return subcoset_lde(ctx, coef, cmap, s.h, w, s.logN, s.b, s.g, shifts.data(), out, sub_tag);
+        lsp::lde(ctx, {.src = coef ? coef : evals, .coeffs = coef != nullptr,
+                       .map = coef ? cmap : ColMap::plain((uint32_t)w), .h = s.h, .w = w, .added_bits = s.lb,
+                       .shifts = shifts.data(), .k0 = s.k0, .nk = s.nk, .out = out});
     }
 
     // the quotient kernel's buffers and arguments (nothing here depends on alpha)
@@ -455,8 +461,7 @@ struct Prover {
             // split: the holder sends its chunks' coefficients (its own inverse
             // NTT), and no rank inverts the whole h x q matrix
             if (s.qsplit && s.g < s.Gq)
-                LSP_HIP(launch_intt(qloc, ColMap::plain((uint32_t)s.cpr), stage + (size_t)s.g * Sq, s.cpr, s.log_h,
-                                    ctx->twiddle29(s.log_h, true), st));
+                intt_device(ctx, qloc, ColMap::plain((uint32_t)s.cpr), stage + (size_t)s.g * Sq, s.cpr, s.log_h);
             for (uint32_t r = 0; r < s.Gq; ++r)
                 comm.bcast(ctx, stage + (size_t)r * Sq, Sq * sizeof(Fr), (int)r,
                            s.qsplit ? "quotient chunk coefficients" : "quotient values");
@@ -480,16 +485,17 @@ struct Prover {
         qlde = ctx->fbuf("q_lde", s.S * q);
         T.begin("coset_lde_batch (quotient)");
         for (size_t j = 0; j < q; ++j) span("coset_lde_batch", 1, h, (int)s.lb);  // one launch, q independent columns
+        const Fr* qcoef = nullptr;
+        ColMap qmap = ColMap::plain((uint32_t)q);
         if (s.qsplit) {  // the chunk coefficients straight from the exchange buffer (column j in slot bitrev(j mod Gq))
-            lde_coeffs_device(ctx, stage, ColMap::blocked(s.logGq, (uint32_t)s.cpr), h, q, s.lb, shifts.data(), qlde,
-                              s.k0, s.nk);
+            qcoef = stage;
+            qmap = ColMap::blocked(s.logGq, (uint32_t)s.cpr);
         } else if (s.sub) {
             Fr* qc = ctx->fbuf("q_coef", h * q);
-            LSP_HIP(launch_intt(qv, ColMap::plain((uint32_t)q), qc, q, s.log_h, ctx->twiddle29(s.log_h, true), st));
-            subcoset_lde(ctx, qc, ColMap::plain((uint32_t)q), h, q, s.logN, s.b, s.g, shifts.data(), qlde, "q_sub");
-        } else {
-            lde_device(ctx, qv, h, q, s.lb, shifts.data(), qlde, s.k0, s.nk);
+            intt_device(ctx, qv, qmap, qc, q, s.log_h);
+            qcoef = qc;
         }
+        rank_lde(qv, qcoef, qmap, q, qlde, "q_sub");
         T.end("coset_lde_batch (quotient)");
         Committed& M = mats[MAT_QUOTIENT];
         M.lde = qlde;

@@ -23,11 +23,26 @@ inline size_t env_size(const char* name, size_t dflt) {
 }
 // ---- lde.cpp
 // two-level power table of `base` covering exponents < 2^bits, cached in the context
-const Fr* pow_table(lsp_ctx* ctx, const std::string& name, const Fr& base, uint32_t bits, uint32_t& L1);
+const Fr* pow_table(lsp_ctx* ctx, const Fr& base, uint32_t bits, uint32_t& L1);
 Fr d2h_fr(lsp_ctx* ctx, const Fr* d);  // one element from the device (synchronises the stream)
-// coset blocks [k0, k0 + nk) of the LDE from h * coefficients (natural order) at `coef`, laid out as `map` says
-void lde_coeffs_device(lsp_ctx* ctx, const Fr* coef, ColMap map, size_t h, size_t w, uint32_t added_bits,
-                       const Fr* shifts_host, Fr* d_out, uint32_t k0, uint32_t nk, bool div_h = true);
+// One device transform to coset evaluations: the coset blocks [k0, k0 + nk)
+// of the bit-reversed LDE of an h x w matrix by 2^added_bits.  Block k = rows
+// k*h .. (k+1)*h - 1 of the full LDE, the evaluations on shift_c *
+// w_N^bitrev(k) * H_h; `out` receives the nk blocks.
+struct LdeRequest {
+    const Fr* src = nullptr;  // the values on H_h, rows in natural order, or (coeffs) h * coefficients, natural
+    bool coeffs = false;      // order: the forward half alone, for ranks that split the inverse
+    ColMap map;               // where the w columns sit in src
+    size_t h = 0, w = 0;
+    uint32_t added_bits = 0;
+    const Fr* shifts = nullptr;  // one per column (host)
+    uint32_t k0 = 0, nk = 0;     // nk = 0: all 2^added_bits blocks
+    bool div_h = true;           // false: src holds true coefficients (coset_dft)
+    Fr* out = nullptr;
+};
+void lde(lsp_ctx* ctx, const LdeRequest& r);
+// the inverse half: out (h x w) <- h * coefficients, natural order, of the w columns `map` picks in `in`
+void intt_device(lsp_ctx* ctx, const Fr* in, ColMap map, Fr* out, size_t w, uint32_t logh);
 // block `blk` (N / 2^b < h rows) of the N-row LDE, folded from the coefficients; buffers named after `tag`
 void subcoset_lde(lsp_ctx* ctx, const Fr* coef, ColMap map, size_t h, size_t w, uint32_t logN, uint32_t b,
                   uint32_t blk, const Fr* shifts_host, Fr* d_out, const std::string& tag);
@@ -129,10 +144,10 @@ size_t host_levels(lsp_ctx* ctx, Fr* host, size_t first, host_clock::time_point*
 // root of a tree whose bottom subtrees live on comm's ranks (`local` = this
 // rank's); `top` gets the host layers above the subtrees
 Fr shard_root(lsp_ctx* ctx, Comm& comm, const Fr& local, std::vector<std::vector<Fr>>& top, const char* tag);
-// coset LDE of an h x w device matrix with per-column shifts -> (h << added_bits) x w bit-reversed rows;
-// with nk > 0 only the coset blocks [k0, k0 + nk) (rows k0*h .. (k0+nk)*h - 1 of the full result)
+// coset LDE of an h x w device matrix with per-column shifts -> (h << added_bits) x w bit-reversed rows
+// (the whole-matrix LdeRequest of the C API and the PCS)
 void lde_device(lsp_ctx* ctx, const Fr* d_in, size_t h, size_t w, uint32_t added_bits, const Fr* shifts_host,
-                Fr* d_out, uint32_t k0 = 0, uint32_t nk = 0);
+                Fr* d_out);
 // TwoAdicSubgroupDft::coset_dft_batch / coset_idft_batch on device matrices (h x w row-major):
 // coefficients -> evaluations on shift H_h stored bit-reversed, and natural-order evaluations -> coefficients
 void coset_dft_device(lsp_ctx* ctx, const Fr* d_coef, size_t h, size_t w, const Fr& shift, Fr* d_out);

@@ -25,24 +25,19 @@ void quotient_domain(lsp_ctx* ctx, uint32_t log_h, uint32_t log_q, uint64_t i0, 
     const Fr GEN = host_generator(), one = fr_one();
     const Fr wh_inv = host_inv_cached(host_two_adic_generator(log_h));
     uint32_t L1Q;
-    const Fr* tabQ = pow_table(ctx, "tabQ", host_two_adic_generator(logQ), logQ, L1Q);
+    const Fr* tabQ = pow_table(ctx, host_two_adic_generator(logQ), logQ, L1Q);
     // 1/((x-1)(x-w_h^-1)) depends on the domain only: cached per shape in the
-    // context (API callers with ever new shapes: a scratch buffer, as lde_twist)
+    // context (API callers with ever new shapes: a scratch buffer, lsp_ctx::table)
     char key[64];
     std::snprintf(key, sizeof key, "qsel_%u_%u_%llu_%u", log_h, logQ, (unsigned long long)i0, log_step);
-    const Fr* inv_den;
-    auto it = ctx->ptabs.find(key);
-    if (it != ctx->ptabs.end()) {
-        inv_den = it->second;
-    } else {
-        const bool keep = ctx->ptabs.size() < 256;
-        Fr* den = ctx->fbuf("q_den", n);
-        Fr* inv = ctx->fbuf(keep ? key : "q_invden", n);
-        LSP_HIP(launch_selector_denoms(tabQ, L1Q, GEN, wh_inv, n, den, st, i0, log_step));
-        LSP_HIP(launch_batch_inverse(den, inv, n, st, ctx->bi_scratch(n)));
-        if (keep) ctx->ptabs[key] = inv;
-        inv_den = inv;
-    }
+    const Fr* inv_den = ctx->table(
+        key, n,
+        [&](Fr* inv) {
+            Fr* den = ctx->fbuf("q_den", n);
+            LSP_HIP(launch_selector_denoms(tabQ, L1Q, GEN, wh_inv, n, den, st, i0, log_step));
+            LSP_HIP(launch_batch_inverse(den, inv, n, st, ctx->bi_scratch(n)));
+        },
+        "q_invden");
     std::vector<Fr> zh(2 * q);  // Z_H on the q cosets of H_h in the quotient domain, then their inverses
     {
         const Fr gh = fr_pow_u64(GEN, h), gq = host_two_adic_generator(log_q);
@@ -88,7 +83,7 @@ void quotient_domain(lsp_ctx* ctx, uint32_t log_h, uint32_t log_q, uint64_t i0, 
 void open_denominators(lsp_ctx* ctx, const Fr& z, const Fr& shift, uint32_t logN, uint64_t row0, size_t n, Fr* out,
                        const Fr* inv_total) {
     uint32_t L1N;
-    const Fr* tabN = pow_table(ctx, "tabN", host_two_adic_generator(logN), logN, L1N);
+    const Fr* tabN = pow_table(ctx, host_two_adic_generator(logN), logN, L1N);
     Fr* den = ctx->fbuf("o_den", n);
     LSP_HIP(launch_open_denoms(z, shift, tabN, L1N, logN, n, den, ctx->stream, row0));
     LSP_HIP(launch_batch_inverse(den, out, n, ctx->stream, ctx->bi_scratch(n), inv_total));
@@ -97,7 +92,7 @@ void open_denominators(lsp_ctx* ctx, const Fr& z, const Fr& shift, uint32_t logN
 void barycentric_sums(lsp_ctx* ctx, const Fr* M, uint32_t w, size_t n, const Fr* inv_den, const Fr& shift,
                       uint32_t logN, uint64_t row0, Fr* sums) {
     uint32_t L1N;
-    const Fr* tabN = pow_table(ctx, "tabN", host_two_adic_generator(logN), logN, L1N);
+    const Fr* tabN = pow_table(ctx, host_two_adic_generator(logN), logN, L1N);
     Fr* partial = ctx->fbuf("o_partial", ((n + 1023) / 1024) * w);
     uint32_t nb = 0;
     LSP_HIP(launch_interp_partial(M, w, n, inv_den, shift, tabN, L1N, logN, partial, &nb, ctx->stream, row0));
@@ -114,7 +109,7 @@ FoldSpec fold_spec(lsp_ctx* ctx, uint32_t logm, uint64_t i0, const Fr& beta) {
     FoldSpec f{};
     f.half = host_inv_cached(fr_from_u64(2));
     f.half_beta = fr_mul(beta, f.half);
-    f.tab = pow_table(ctx, "tabF", host_inv_cached(host_two_adic_generator(logm + 1)), logm, f.L1);
+    f.tab = pow_table(ctx, host_inv_cached(host_two_adic_generator(logm + 1)), logm, f.L1);
     f.logm = logm;
     f.i0 = i0;
     return f;

@@ -124,3 +124,54 @@ def test_bad_arguments(gpu_ctx):
     with pytest.raises(_lib.LspError) as e:
         gpu_ctx.coset_idft_batch(m, mont([0])[0])
     assert e.value.code == _lib.LSP_E_ARG
+
+
+@pytest.fixture(scope="module")
+def lde_ctx(product_lib):
+    """a context of its own: the many shifts below fill its twist-table cache, not the suite's"""
+    from linea_stark_prover_amd.prover import Context, StarkConfig
+    ctx = Context(StarkConfig())
+    yield ctx
+    ctx.close()
+
+
+def _lde(ctx, mat, added_bits, shifts, per_column):
+    """lsp_coset_lde_batch (one shift) or lsp_coset_lde_batch_shifts (one per column), host memory"""
+    import ctypes
+    from linea_stark_prover_amd import _lib as L
+    h, w = mat.shape[0], mat.shape[1]
+    mat, shifts = np.ascontiguousarray(mat), np.ascontiguousarray(shifts)
+    out = np.zeros((h << added_bits, w, 4), np.uint64)
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    fn = L.lib().lsp_coset_lde_batch_shifts if per_column else L.lib().lsp_coset_lde_batch
+    assert shifts.shape == ((w, 4) if per_column else (4,))
+    L.check(fn(ctx.h, ptr(mat), h, w, added_bits, ptr(shifts), ptr(out), L.LSP_MEM_HOST), ctx.h)
+    return out
+
+
+@pytest.mark.parametrize("logh,w", [(1, 1), (2, 3), (3, 9), (5, 8), (10, 3), (11, 9), (12, 2)])
+def test_lde_forms_agree(lde_ctx, logh, w):
+    """The smallest shapes at which each branch of the LDE runs -- one pass with
+    the bit-reversed gather (logh <= 10), two passes (11, 12), odd k with its lone
+    radix-2 stage, a last chunk with padding columns (w = 3, 9), one coset without
+    the chain (added_bits 0) and several with it: one shift for the batch equals
+    w copies of it given per column, bit for bit; with w distinct shifts every
+    column equals the one-column call with its own shift (the per-column twist
+    tables against the row factors); and up to logh = 11 the batch equals the
+    Python oracle's coset NTT."""
+    rng = np.random.default_rng(100 * logh + w)
+    h = 1 << logh
+    mat = rand_fr(rng, (h, w))
+    svals = [int.from_bytes(rng.bytes(32), "little") % P for _ in range(w)]
+    shifts = mont(svals)
+    cols = cols_of(mat) if logh <= 11 else None
+    for added in (0, 1, 3):
+        one = _lde(lde_ctx, mat, added, shifts[0], False)
+        assert np.array_equal(one, _lde(lde_ctx, mat, added, np.repeat(shifts[:1], w, axis=0), True)), added
+        each = _lde(lde_ctx, mat, added, shifts, True)
+        for c in range(w):
+            col = _lde(lde_ctx, mat[:, c:c + 1], added, shifts[c], False)
+            assert np.array_equal(each[:, c], col[:, 0]), (added, c)
+        if cols is not None:
+            exp = [O.coset_lde_column(col, added, svals[0]) for col in cols]
+            assert ints(one.reshape(-1, 4)) == [exp[c][i] for i in range(h << added) for c in range(w)], added

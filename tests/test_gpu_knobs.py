@@ -6,7 +6,8 @@ Merkle levels on the host or the GPU (LSP_HOST_TREE_TOP), FRI rounds on the
 host (LSP_FRI_HOST_TAIL), when the host pool starts spinning for a tree top
 (LSP_TOP_WARM), row / quad / pair / one-lane permutations for narrow
 levels (LSP_ROW_MAX, LSP_COOP_MAX, LSP_PAIR_MAX), zero-copy tree tops, host subtree tasks, LDE pass
-plans (LSP_NTT_KMAX, LSP_NTT_LOGCW, LSP_NTT_TWL), the host pool size and the
+plans (LSP_NTT_KMAX, LSP_NTT_LOGCW, LSP_NTT_TWL), every coset block twisted from
+its own table (LSP_NTT_CHAIN=0), the host pool size and the
 IFMA host batches.  Several are read once per process, so each setting runs in a
 child process; the per-call knobs vary inside each child.  The default proof is
 pinned to the oracle elsewhere (test_gpu_fullsize.py, test_gpu_parity.py), so
@@ -59,6 +60,7 @@ SETTINGS = {
     "no_top_warm": {"LSP_TOP_WARM": "0"},
     "top_warm_64k": {"LSP_TOP_WARM": "65536"},
     "lde_plans": {"LSP_NTT_KMAX": "7", "LSP_NTT_LOGCW": "3", "LSP_NTT_TWL": "0"},
+    "lde_unchained": {"LSP_NTT_CHAIN": "0"},
     "host_serial_scalar": {"LSP_HOST_THREADS": "1", "LSP_HOST_IFMA": "0"},
 }
 

@@ -58,7 +58,7 @@ def test_coset_lde_matches_oracle(gpu_ctx, oracle_lib, logh, w, added):
 
 
 def test_coset_lde_wide_plan(gpu_ctx, oracle_lib):
-    """From 48 columns launch_lde plans 8-column chunks: 2^19 x 50 runs as
+    """From 48 columns plan_ntt plans 8-column chunks: 2^19 x 50 runs as
     [7,6,6] (whole 256-byte row segments, a partial last chunk of 2) instead of
     [10,9].  Columns transform independently, so the oracle checks a few of
     them, from the first chunk, a chunk boundary and the partial chunk."""

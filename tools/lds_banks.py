@@ -19,7 +19,7 @@ by a data-dependent quotient q, drawn here from a uniform range.
 
     python tools/lds_banks.py [--swizzle none|ntt|pad|xor] [--qrange 17]
 
-(none: round 5's layout; ntt: the shipped tswz map + the planar q r table.)
+(none: round 5's layout; ntt: the XOR map measured in round 6, docs/HISTORY.md F, + the planar q r table.)
 
 Prints extra cycles per LDS instruction for each access site and in total,
 the figure SQ_LDS_BANK_CONFLICT / SQ_INSTS_LDS measures (profiles/r05l_valu_pmc.txt:
@@ -75,7 +75,7 @@ class Model:
         if self.swz == "ntt5":  # the first map tried (5 source bits, ~11 VALU ops)
             x = e ^ ((e >> 2) & 0x1A)
             return x ^ (0xD if (e >> 4) & 1 else 0) ^ (0xE if (e >> 7) & 1 else 0)
-        if self.swz == "ntt":  # k_ntt.hip tswz (the shipped map: two shift-mask terms)
+        if self.swz == "ntt":  # the round-6 XOR map of the NTT tile (two shift-mask terms; measured, not shipped)
             return e ^ ((e >> 1) & 8) ^ ((e >> 2) & 31)
         return e
 
@@ -177,7 +177,7 @@ def main():
     ap.add_argument("--swizzle", default="none")
     ap.add_argument("--qrange", type=int, default=17)
     a = ap.parse_args()
-    # the three passes of a 2^19 x 8 LDE (run_lde: ks = [10, 9])
+    # the three passes of a 2^19 x 8 LDE (plan_ntt: ks = [10, 9])
     for name, k, logG, logCW, dif, qt in (("k_ntt_rm<false,1,0> (inverse first, k=10)", 10, 0, 0, False, True),
                                           ("k_ntt_rm<true,2,1> fused (k=9, CW=2), forward stages", 9, 0, 1, True, False),
                                           ("k_ntt_rm<true,0,0> in place (k=10)", 10, 0, 0, True, True)):
