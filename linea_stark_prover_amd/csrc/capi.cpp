@@ -1662,20 +1662,7 @@ int lsp_calibrate_poseidon2(lsp_ctx* ctx, double* mperm_per_s) {
         LSP_REQUIRE(ctx && mperm_per_s, LSP_E_ARG, "null");
         std::lock_guard<std::mutex> g(ctx->mu);
         need_gpu(ctx);
-        // the peak: best of several grid sizes (2..32 blocks of 256 lanes per CU)
-        const uint32_t iters = 4;
-        Fr* out = ctx->fbuf("calib", (size_t)256 * 256 * 32);
-        LSP_HIP(launch_calib_perm(out, (size_t)256 * 256 * 4, 1, ctx->rc29_dev, ctx->p2.L, ctx->stream));  // warm
-        StreamTimer timer;
-        double best = 0;
-        for (size_t per_cu : {2, 4, 8, 16, 32}) {
-            const size_t nth = (size_t)256 * 256 * per_cu;
-            const float ms = timer.ms(ctx->stream, [&] {
-                LSP_HIP(launch_calib_perm(out, nth, iters, ctx->rc29_dev, ctx->p2.L, ctx->stream));
-            });
-            best = std::max(best, (double)nth * iters / (ms * 1e-3) / 1e6);
-        }
-        *mperm_per_s = best;
+        *mperm_per_s = calibrate_poseidon2(ctx);
     });
 }
 

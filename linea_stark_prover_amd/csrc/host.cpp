@@ -445,6 +445,9 @@ lsp_ctx::~lsp_ctx() {
     if (ev_near) (void)hipEventDestroy(ev_near);
     if (ev_top) (void)hipEventDestroy(ev_top);
     if (ev_warm) (void)hipEventDestroy(ev_warm);
+    if (ev_slice_in) (void)hipEventDestroy(ev_slice_in);
+    if (ev_slice) (void)hipEventDestroy(ev_slice);
+    if (ev_slice_up) (void)hipEventDestroy(ev_slice_up);
     if (side_stream) {
         (void)hipStreamSynchronize(side_stream);
         (void)hipEventDestroy(ev_wide);

@@ -520,6 +520,15 @@ struct lsp_ctx {
     std::map<std::string, hipEvent_t> stage_ev;  // last copy out of each h2d_async staging buffer
     hipEvent_t ev_near = nullptr, ev_top = nullptr;  // tree-top hand-off (merkle.cpp commit_device)
     hipEvent_t ev_warm = nullptr;  // after a tree's wide levels: the host pool starts spinning (commit_device)
+    // the host slice of a big tree (host_slice.hpp; commit_device): the tree's
+    // input is complete / the slice's rows are in pinned memory; and the two
+    // rates its plan compares, permutations per second, measured once (0: not yet)
+    hipEvent_t ev_slice_in = nullptr, ev_slice = nullptr;
+    double slice_host_perm_s = 0, slice_gpu_perm_s = 0;
+    // a proof's slice layers go up on the side stream as soon as they are made;
+    // ev_slice_up follows the last of them (flush_top_uploads waits for it)
+    hipEvent_t ev_slice_up = nullptr;
+    bool slice_uploads_pending = false;
     // work beside a tree's narrow levels (prove.cpp, "constraints before alpha"):
     // a low-priority stream, the event after the tree's wide levels it waits
     // for, and the event the main stream waits for before using its results

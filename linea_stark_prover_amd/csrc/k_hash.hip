@@ -272,10 +272,11 @@ hipError_t launch_merkle_level(const Fr* src, Fr* dst, size_t nout, const F29* r
 }
 
 hipError_t launch_merkle_levels(Fr* layers, size_t nleaves, size_t stop_len, const F29* rc, P2Layout L,
-                                size_t* off_out, size_t* len_out, hipStream_t st) {
+                                size_t* off_out, size_t* len_out, hipStream_t st, uint32_t skip_log_frac) {
     size_t off = 0, len = nleaves;
     while (len > stop_len && len > 1) {
-        hipError_t e = launch_merkle_level(layers + off, layers + off + len, len / 2, rc, L, st);
+        const size_t nout = len / 2, skip = skip_log_frac ? nout >> skip_log_frac : 0;
+        hipError_t e = launch_merkle_level(layers + off, layers + off + len, nout - skip, rc, L, st);
         if (e != hipSuccess) return e;
         off += len;
         len /= 2;

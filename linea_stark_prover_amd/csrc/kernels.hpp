@@ -126,9 +126,11 @@ hipError_t launch_grind(const Fr pre[3], uint32_t wlane, uint64_t base, uint64_t
 // full tree above the leaf digests already stored at layers[0..nleaves)
 hipError_t launch_merkle_tree(Fr* layers, size_t nleaves, const F29* rc29, P2Layout L, hipStream_t st);
 // the levels above the leaves while the current layer is longer than stop_len;
-// *off_out / *len_out = offset and length of the last layer written
+// *off_out / *len_out = offset and length of the last layer written.
+// skip_log_frac k > 0: only the first len - (len >> k) digests of every layer
+// (the last part is the host slice's, host_slice.hpp; len >> k >= 1 throughout)
 hipError_t launch_merkle_levels(Fr* layers, size_t nleaves, size_t stop_len, const F29* rc29, P2Layout L,
-                                size_t* off_out, size_t* len_out, hipStream_t st);
+                                size_t* off_out, size_t* len_out, hipStream_t st, uint32_t skip_log_frac = 0);
 
 // --------------------------------------------------- k_merkle_inject.hip
 // dst[i] = compress(compress(src[2i], src[2i+1]), inj[i]) for i < nout: a level

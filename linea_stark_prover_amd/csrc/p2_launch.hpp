@@ -42,7 +42,11 @@ inline void state_grid(size_t n, int lanes, unsigned& blocks, unsigned& bs) {
     // 4 lanes per state.  At 16K states (one wave per SIMD of the chip) 64-lane
     // blocks land two waves on some SIMDs (~2x the level's latency); 256-lane
     // blocks, one per CU, spread them one per SIMD.  Narrower levels: 64.
-    bs = lanes == 4 ? (coop_bs() ? coop_bs() : (4 * n >= 65536 ? 256u : 64u)) : 256u;
+    // "At 16K" is every count above 8K: beside a host slice (host_slice.hpp) that
+    // level has 16384 - (16384 >> k) states, and 64-lane blocks took its three
+    // launches per 2^19 proof to about twice their time (+0.18 ms per proof in
+    // the kernel trace).  Powers of two get the block size they had.
+    bs = lanes == 4 ? (coop_bs() ? coop_bs() : (n > 8192 ? 256u : 64u)) : 256u;
     blocks = nblocks((size_t)lanes * n, bs);
 }
 

@@ -136,6 +136,19 @@ struct DeferTopUploads {
     ~DeferTopUploads();
 };
 void flush_top_uploads(lsp_ctx* ctx);
+// the GPU's Poseidon2 peak, M permutations/s: register-resident chains, the
+// best of several grid sizes (lsp_calibrate_poseidon2; the host slice's plan)
+double calibrate_poseidon2(lsp_ctx* ctx);
+// The host slice's plumbing (host_slice.hpp), shared by the two owners of a
+// tree.  slice_stream_begin: the side stream, made to wait for all the main
+// stream holds so far (what makes the tree's input); the caller queues the
+// downloads of the slice's rows on it, then slice_stream_end records
+// ctx->ev_slice behind them.
+hipStream_t slice_stream_begin(lsp_ctx* ctx);
+void slice_stream_end(lsp_ctx* ctx);
+// out[i] = the sponge of row i of the n host matrices side by side, i in [i0, i1)
+void host_hash_rows(const P2Host& p2, const Fr* const* rows, const size_t* width, size_t n, Fr* out, size_t i0,
+                    size_t i1);
 // the levels above `first` digests host[0, first) on the host pool; returns the
 // end of the layers.  pairs (optional): the digests are made first, as
 // compress(pairs[2i], pairs[2i+1])
@@ -167,6 +180,9 @@ size_t host_tree_top(const lsp_ctx* ctx);
 // the leaves and the wide levels (every level of more than 2^15 digests): work
 // queued behind it on another stream fills the chip beside the narrow levels
 // and the host's tree top
+// A big tree inside a lone proof (or any, under LSP_HOST_SLICE) has a host slice
+// (host_slice.hpp): the pool hashes the last leaves >> k leaves and their
+// subtree down to the layer of `top` digests while the GPU takes the prefix
 Fr commit_device(lsp_ctx* ctx, const MatList& m, size_t height, Fr* layers, size_t top, const FoldSpec* fold = nullptr,
                  const std::function<void(hipEvent_t)>* side = nullptr);
 // Mixed-height batches (merkle_mixed.cpp; U14).  A class = the matrices of one
