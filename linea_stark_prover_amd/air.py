@@ -8,6 +8,7 @@ the constraint order of ``LineaAIR::eval`` (air/src/lib.rs:47-167).
 """
 from __future__ import annotations
 
+import itertools
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple, Union
 
@@ -22,6 +23,14 @@ class AirPermutationConfig:
     b_columns_ids: List[int]
     b_inverse_id: int
     check_id: int
+
+    @staticmethod
+    def block(na: int, nb: int, col0: int = 0) -> "AirPermutationConfig":
+        """A witness block's config, its first column ``col0``: a.., b.., b_inverse,
+        check (trace/src/permutation.rs:81-90; csrc/witness_layout.hpp's PermBlock)."""
+        ids = itertools.count(col0)
+        return AirPermutationConfig([next(ids) for _ in range(na)], [next(ids) for _ in range(nb)], next(ids),
+                                    next(ids))
 
     def shift(self, shift: int) -> None:
         self.a_columns_ids = [i + shift for i in self.a_columns_ids]
@@ -62,6 +71,19 @@ class AirLookupConfig:
     b_inverses_id: List[int]
     occurrences_id: List[int]
     check_id: int
+
+    @staticmethod
+    def block(na: int, nt: int, nbc: int, col0: int = 0) -> "AirLookupConfig":
+        """A witness block's config, its first column ``col0``: a.., tables.., a_filter,
+        b_filters.., a_inverse, b_inverses.., multiplicities.., sum
+        (trace/src/lookup.rs:178-214; csrc/witness_layout.hpp's LookupBlock)."""
+        ids = itertools.count(col0)
+
+        def take(k):
+            return [next(ids) for _ in range(k)]
+
+        return AirLookupConfig(take(na), [take(nbc) for _ in range(nt)], next(ids), take(nt), next(ids), take(nt),
+                               take(nt), next(ids))
 
     def shift(self, shift: int) -> None:
         self.a_columns_ids = [i + shift for i in self.a_columns_ids]
@@ -464,5 +486,4 @@ def lower(air: LineaAIR, which=None) -> LineaAIR:
 def permutation_air(ncols: int) -> LineaAIR:
     """The benchmark AIR: one permutation group of ncols 'from' + ncols 'to'
     columns (trace/src/permutation.rs:81-90 column layout)."""
-    return LineaAIR([AirPermutationConfig(list(range(ncols)), list(range(ncols, 2 * ncols)), 2 * ncols,
-                                          2 * ncols + 1)])
+    return LineaAIR([AirPermutationConfig.block(ncols, ncols)])

@@ -1,4 +1,5 @@
-// extern "C" entry points of liblsp_hip.so (declared in include/lsp.h).
+// extern "C" entry points of liblsp_hip.so (declared in include/lsp.h); the
+// witness, raw-trace and trace-generator ones are in witness.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -7,18 +8,18 @@
 #include <memory>
 #include <thread>
 
+#include "capi_internal.hpp"
 #include "comm.hpp"
-#include "prove_internal.hpp"
+#include "splitmix.hpp"
 
 using namespace lsp;
 
-namespace {
-thread_local std::string g_err;  // errors without a context
+thread_local std::string lsp::g_err;
 
 #ifdef LSP_DEBUG_BOUNDS
 // The debug build: every kernel translation unit's fault word after a C-ABI
 // call (dbg_bounds.hpp), with its (file code, line) mapped back to a name
-std::string bounds_fault_report() {
+std::string lsp::bounds_fault_report() {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return "";
     (void)hipDeviceSynchronize();  // the call's kernels are done (any stream)
@@ -46,38 +47,12 @@ std::string bounds_fault_report() {
     }
     return out;
 }
-#endif
 
-}  // namespace
-
-#ifdef LSP_DEBUG_BOUNDS
 void lsp::dbg_check_after(const char* what) {
     const std::string bad = bounds_fault_report();
     if (!bad.empty()) throw LspError(LSP_E_STATE, bad + " after " + what);
 }
 #endif
-
-namespace {
-template <class F>
-int guarded(lsp_ctx* ctx, F&& f) {
-    try {
-        f();
-#ifdef LSP_DEBUG_BOUNDS
-        const std::string bad = bounds_fault_report();
-        if (!bad.empty()) throw LspError(LSP_E_STATE, bad);
-#endif
-        return LSP_OK;
-    } catch (const LspError& e) {
-        (ctx ? ctx->err : g_err) = e.what();
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        (ctx ? ctx->err : g_err) = "host allocation failed";
-        return LSP_E_OOM;
-    } catch (const std::exception& e) {
-        (ctx ? ctx->err : g_err) = e.what();
-        return LSP_E_STATE;
-    }
-}
 
 // device input: either the caller's device pointer or a pool copy of host data.
 // The host copy is one pageable hipMemcpyAsync: it moves a 2^19 x 8 trace at
@@ -86,7 +61,7 @@ int guarded(lsp_ctx* ctx, F&& f) {
 // fresh buffer is counted), and faster than staging through a pinned ring
 // filled by host threads (37-46): tools/ubench/h2d.hip, profiles/r05b_h2d.json,
 // r05c_h2d.json; in-proof A/B tools/time_upload.py, profiles/r05c_time_upload.txt
-const Fr* dev_in(lsp_ctx* ctx, const lsp_fr* p, size_t n, int mem, const char* name) {
+const Fr* lsp::dev_in(lsp_ctx* ctx, const lsp_fr* p, size_t n, int mem, const char* name) {
     LSP_REQUIRE(p || n == 0, LSP_E_ARG, "null input pointer");
     if (mem == LSP_MEM_DEVICE) return reinterpret_cast<const Fr*>(p);
     LSP_REQUIRE(mem == LSP_MEM_HOST, LSP_E_ARG, "mem must be LSP_MEM_HOST or LSP_MEM_DEVICE");
@@ -94,6 +69,14 @@ const Fr* dev_in(lsp_ctx* ctx, const lsp_fr* p, size_t n, int mem, const char* n
     if (n) LSP_HIP(hipMemcpyAsync(d, p, n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
     return d;
 }
+
+void lsp::need_gpu(lsp_ctx* ctx) {
+    LSP_REQUIRE(ctx, LSP_E_ARG, "null ctx");
+    LSP_REQUIRE(ctx->device != LSP_HOST_ONLY, LSP_E_STATE, "host-only context (LSP_HOST_ONLY) has no GPU");
+    LSP_HIP(hipSetDevice(ctx->device));
+}
+
+namespace {
 Fr* dev_out(lsp_ctx* ctx, lsp_fr* p, size_t n, int mem, const char* name) {
     LSP_REQUIRE(p || n == 0, LSP_E_ARG, "null output pointer");
     if (mem == LSP_MEM_DEVICE) return reinterpret_cast<Fr*>(p);
@@ -111,43 +94,6 @@ std::vector<Fr> to_frs(const lsp_fr* p, size_t n) {
     for (size_t i = 0; i < n; ++i) v[i] = to_fr(p[i]);
     return v;
 }
-
-void need_gpu(lsp_ctx* ctx) {
-    LSP_REQUIRE(ctx, LSP_E_ARG, "null ctx");
-    LSP_REQUIRE(ctx->device != LSP_HOST_ONLY, LSP_E_STATE, "host-only context (LSP_HOST_ONLY) has no GPU");
-    LSP_HIP(hipSetDevice(ctx->device));
-}
-
-struct SplitMix64 {
-    uint64_t s;
-    uint64_t next() {
-        uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        return z ^ (z >> 31);
-    }
-    // U4: 4 words -> 253-bit mask -> reject >= r
-    Fr fr() {
-        for (;;) {
-            Fr c;
-            for (int k = 0; k < 4; ++k) {
-                uint64_t x = next();
-                c.v[2 * k] = (uint32_t)x;
-                c.v[2 * k + 1] = (uint32_t)(x >> 32);
-            }
-            c.v[7] &= (1u << 29) - 1;
-            if (fr_words_lt_mod(c)) return fr_from_canonical(c);
-        }
-    }
-    uint64_t below(uint64_t n) {
-        const unsigned __int128 two64 = (unsigned __int128)1 << 64;
-        const unsigned __int128 lim = two64 - (two64 % n);
-        for (;;) {
-            uint64_t x = next();
-            if ((unsigned __int128)x < lim) return x % n;
-        }
-    }
-};
 }  // namespace
 
 extern "C" {
@@ -1509,154 +1455,6 @@ int lsp_calibrate_fr_mul(lsp_ctx* ctx, double* gmul_per_s) {
     });
 }
 
-// ------------------------------------------------- witness generation (F1)
-extern "C++" {
-namespace {
-// the block's rows: straight into a device trace, or via a scratch block and a
-// strided copy into a host trace
-template <class F>
-void witness_block(lsp_ctx* ctx, lsp_fr* trace, size_t n, size_t trace_w, size_t col0, size_t bw, int mem, F&& fill) {
-    LSP_REQUIRE(trace && col0 + bw <= trace_w, LSP_E_ARG, "witness block outside the trace width");
-    if (mem == LSP_MEM_DEVICE) {
-        fill(reinterpret_cast<Fr*>(trace) + col0, trace_w);
-        return;
-    }
-    Fr* blk = ctx->fbuf("wit_block", n * bw);
-    fill(blk, bw);
-    LSP_HIP(hipMemcpy2DAsync(reinterpret_cast<Fr*>(trace) + col0, trace_w * sizeof(Fr), blk, bw * sizeof(Fr),
-                             bw * sizeof(Fr), n, hipMemcpyDeviceToHost, ctx->stream));
-    ctx->sync();
-}
-}  // namespace
-}
-
-int lsp_witness_permutation(lsp_ctx* ctx, const lsp_fr* a, uint32_t na, const lsp_fr* b, uint32_t nb, size_t n,
-                            const lsp_fr* alpha, const lsp_fr* delta, lsp_fr* trace, size_t trace_w, size_t col0,
-                            int mem) {
-    return guarded(ctx, [&] {
-        LSP_REQUIRE(ctx && alpha && delta && na >= 1 && nb >= 1 && n >= 1, LSP_E_ARG, "bad witness arguments");
-        std::lock_guard<std::mutex> g(ctx->mu);
-        need_gpu(ctx);
-        const Fr* da = dev_in(ctx, a, (size_t)na * n, mem, "wit_a");
-        const Fr* db = dev_in(ctx, b, (size_t)nb * n, mem, "wit_b");
-        const Fr al = to_fr(*alpha), de = to_fr(*delta);
-        witness_block(ctx, trace, n, trace_w, col0, (size_t)na + nb + 2, mem, [&](Fr* out, size_t stride) {
-            witness_permutation_device(ctx, da, na, db, nb, n, al, de, out, stride);
-        });
-    });
-}
-
-int lsp_gen_permutation_trace_device(lsp_ctx* ctx, uint64_t seed, uint32_t log_n, uint32_t ncols,
-                                     const lsp_fr* alpha, const lsp_fr* delta, lsp_fr* trace) {
-    return guarded(ctx, [&] {
-        LSP_REQUIRE(ctx && alpha && delta && trace && ncols >= 1 && log_n >= 1 && log_n <= 30, LSP_E_ARG,
-                    "bad device trace-generator arguments");
-        std::lock_guard<std::mutex> g(ctx->mu);
-        need_gpu(ctx);
-        const size_t n = (size_t)1 << log_n;
-        Fr* a = ctx->fbuf("gen_a", (size_t)ncols * n);
-        Fr* b = ctx->fbuf("gen_b", (size_t)ncols * n);
-        // the row bijection i -> (mul i + add) mod n: mul odd, both from the seed
-        const uint64_t mul = ((seed * 0xD1B54A32D192ED03ull) ^ 0x5851F42D4C957F2Dull) | 1u;
-        const uint64_t add = seed * 0xA24BAED4963EE407ull + 0x9FB21C651E98DF25ull;
-        LSP_HIP(launch_gen_raw_perm(seed, n, ncols, mul, add, a, b, ctx->stream));
-        witness_permutation_device(ctx, a, ncols, b, ncols, n, to_fr(*alpha), to_fr(*delta), (Fr*)trace,
-                                   2 * (size_t)ncols + 2);
-        ctx->release("gen_");
-        ctx->release("wit_");
-    });
-}
-
-int lsp_witness_lookup(lsp_ctx* ctx, const lsp_fr* a, uint32_t na, const lsp_fr* b, uint32_t ntables, uint32_t nbc,
-                       const lsp_fr* a_filter, const lsp_fr* b_filter, size_t n, const lsp_fr* alpha,
-                       const lsp_fr* delta, lsp_fr* trace, size_t trace_w, size_t col0, int mem) {
-    return guarded(ctx, [&] {
-        LSP_REQUIRE(ctx && alpha && delta && na >= 1 && ntables >= 1 && nbc >= 1 && n >= 1, LSP_E_ARG,
-                    "bad witness arguments");
-        std::lock_guard<std::mutex> g(ctx->mu);
-        need_gpu(ctx);
-        const Fr* da = dev_in(ctx, a, (size_t)na * n, mem, "wit_a");
-        const Fr* db = dev_in(ctx, b, (size_t)ntables * nbc * n, mem, "wit_b");
-        const Fr* daf = dev_in(ctx, a_filter, n, mem, "wit_af");
-        const Fr* dbf = dev_in(ctx, b_filter, (size_t)ntables * n, mem, "wit_bf");
-        const Fr al = to_fr(*alpha), de = to_fr(*delta);
-        const size_t bw = (size_t)na + (size_t)ntables * (nbc + 3) + 3;
-        witness_block(ctx, trace, n, trace_w, col0, bw, mem, [&](Fr* out, size_t stride) {
-            witness_lookup_device(ctx, da, na, db, ntables, nbc, daf, dbf, n, al, de, out, stride);
-        });
-    });
-}
-
-// ------------------------------------------------------ trace input (F4)
-int lsp_raw_trace_parse(const uint8_t* cbor, size_t len, lsp_raw_trace** out) {
-    return guarded(nullptr, [&] {
-        LSP_REQUIRE(cbor && out, LSP_E_ARG, "null input");
-        *out = parse_raw_trace(cbor, len);
-    });
-}
-
-int lsp_raw_trace_shape(const lsp_raw_trace* t, int* kind, uint32_t* na, uint32_t* ntables, uint32_t* nbc,
-                        size_t* max_height, size_t* width) {
-    return guarded(nullptr, [&] {
-        LSP_REQUIRE(t, LSP_E_ARG, "null trace");
-        size_t h, w;
-        raw_trace_shape(*t, h, w);
-        if (kind) *kind = t->kind;
-        if (na) *na = (uint32_t)t->a.size();
-        if (ntables) *ntables = t->ntables;
-        if (nbc) *nbc = t->nbc;
-        if (max_height) *max_height = h;
-        if (width) *width = w;
-    });
-}
-
-int lsp_raw_trace_columns(const lsp_raw_trace* t, size_t height, lsp_fr* out, size_t cap, size_t* n) {
-    return guarded(nullptr, [&] {
-        LSP_REQUIRE(t && n, LSP_E_ARG, "null argument");
-        const std::vector<Fr> cols = raw_trace_columns(*t, height);
-        *n = cols.size();
-        if (out) {
-            LSP_REQUIRE(cap >= cols.size(), LSP_E_ARG, "buffer too small");
-            std::memcpy(out, cols.data(), cols.size() * sizeof(Fr));
-        }
-    });
-}
-
-int lsp_raw_trace_push(lsp_ctx* ctx, const lsp_raw_trace* t, size_t height, const lsp_fr* alpha, const lsp_fr* delta,
-                       lsp_fr* trace, size_t trace_w, size_t col0, int mem) {
-    return guarded(ctx, [&] {
-        LSP_REQUIRE(ctx && t && alpha && delta && height >= 1, LSP_E_ARG, "bad raw trace push arguments");
-        std::lock_guard<std::mutex> g(ctx->mu);
-        need_gpu(ctx);
-        const std::vector<Fr> cols = raw_trace_columns(*t, height);  // RawTrace resize: zero words
-        Fr* d = ctx->fbuf("raw_cols", cols.size());
-        LSP_HIP(hipMemcpyAsync(d, cols.data(), cols.size() * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-        const Fr al = to_fr(*alpha), de = to_fr(*delta);
-        const uint32_t na = (uint32_t)t->a.size();
-        size_t h, w;
-        raw_trace_shape(*t, h, w);
-        if (t->kind == LSP_AIR_PERMUTATION) {
-            const uint32_t nb = (uint32_t)t->b.size();
-            witness_block(ctx, trace, height, trace_w, col0, w, mem, [&](Fr* out, size_t stride) {
-                witness_permutation_device(ctx, d, na, d + (size_t)na * height, nb, height, al, de, out, stride);
-            });
-        } else {
-            const Fr* b = d + (size_t)na * height;
-            const Fr* af = b + (size_t)t->ntables * t->nbc * height;
-            const Fr* bf = af + height;
-            witness_block(ctx, trace, height, trace_w, col0, w, mem, [&](Fr* out, size_t stride) {
-                witness_lookup_device(ctx, d, na, b, t->ntables, t->nbc, af, bf, height, al, de, out, stride);
-            });
-        }
-        ctx->sync();  // `cols` must outlive the upload
-    });
-}
-
-int lsp_raw_trace_free(lsp_raw_trace* t) {
-    delete t;
-    return LSP_OK;
-}
-
 int lsp_calibrate_poseidon2(lsp_ctx* ctx, double* mperm_per_s) {
     return guarded(ctx, [&] {
         LSP_REQUIRE(ctx && mperm_per_s, LSP_E_ARG, "null");
@@ -1675,57 +1473,6 @@ int lsp_calibrate_intt(lsp_ctx* ctx, uint32_t log_h, size_t w, double* gelem_per
         need_gpu(ctx);
         *gelem_per_s = calibrate_intt(ctx, log_h, w, 5, nullptr);
         ctx->release("calib_intt_");
-    });
-}
-
-int lsp_gen_permutation_trace(uint64_t seed, uint32_t log_n, uint32_t ncols, const lsp_fr* alpha,
-                              const lsp_fr* delta, int small_values, lsp_fr* rows) {
-    return guarded(nullptr, [&] {
-        LSP_REQUIRE(alpha && delta && rows && ncols >= 1 && log_n >= 1 && log_n <= 30, LSP_E_ARG,
-                    "bad trace arguments");
-        const size_t n = (size_t)1 << log_n, w = 2 * (size_t)ncols + 2;
-        SplitMix64 g{seed ^ 0x5452414345ull};  // "TRACE"
-        std::vector<Fr> a((size_t)ncols * n);
-        for (uint32_t c = 0; c < ncols; ++c)
-            for (size_t i = 0; i < n; ++i)
-                a[c * n + i] = small_values ? fr_from_u64(g.next() & 0xFFFFFFFFull) : g.fr();
-        std::vector<size_t> perm(n);
-        for (size_t i = 0; i < n; ++i) perm[i] = i;
-        for (size_t i = n - 1; i > 0; --i) std::swap(perm[i], perm[g.below(i + 1)]);
-        const Fr al = to_fr(*alpha), dl = to_fr(*delta);
-        std::vector<Fr> den(n), inv(n);
-        for (size_t i = 0; i < n; ++i) {
-            Fr bc = fr_zero();
-            for (uint32_t c = 0; c < ncols; ++c) bc = fr_add(fr_mul(bc, al), a[c * n + perm[i]]);
-            den[i] = fr_add(bc, dl);
-        }
-        // batch inverse (RawPermutationTrace::get_trace inverts per row; same values)
-        Fr acc = fr_one();
-        for (size_t i = 0; i < n; ++i) {
-            inv[i] = acc;
-            acc = fr_mul(acc, den[i]);
-        }
-        Fr ia = fr_inv(acc);
-        for (size_t i = n; i-- > 0;) {
-            const Fr t = fr_mul(ia, inv[i]);
-            ia = fr_mul(ia, den[i]);
-            inv[i] = t;
-        }
-        Fr prev = fr_one();
-        for (size_t i = 0; i < n; ++i) {
-            Fr* row = reinterpret_cast<Fr*>(rows) + i * w;
-            Fr ac = fr_zero();
-            for (uint32_t c = 0; c < ncols; ++c) {
-                row[c] = a[c * n + i];
-                row[ncols + c] = a[c * n + perm[i]];
-                ac = fr_add(fr_mul(ac, al), row[c]);
-            }
-            row[2 * ncols] = inv[i];
-            prev = fr_mul(fr_mul(prev, fr_add(ac, dl)), inv[i]);
-            row[2 * ncols + 1] = prev;
-        }
-        LSP_REQUIRE(fr_eq(prev, fr_one()), LSP_E_STATE,
-                    "failed to check constrain: check column should be 1 on the last row");
     });
 }
 

@@ -272,26 +272,27 @@ void raw_trace_shape(const lsp_raw_trace& t, size_t& height, size_t& width) {
     height = 0;
     for (auto& c : t.a) height = std::max(height, c.size());
     for (auto& c : t.b) height = std::max(height, c.size());
-    if (t.kind == LSP_AIR_LOOKUP)
-        width = t.a.size() + (size_t)t.ntables * (t.nbc + 3) + 3;
-    else
-        width = t.a.size() + t.b.size() + 2;
+    width = t.kind == LSP_AIR_LOOKUP ? t.lookup().width() : t.perm().width();
 }
 
-// the columns resized to `height` (Vec::resize with zero words), column-major:
-// a.., b.. (lookup: table-major), then for a lookup a_filter, b_filters..
+// the columns resized to `height` (Vec::resize with zero words), column-major
+// at the block's raw offsets (lookup b: table-major).  Filters beyond a
+// lookup's tables follow the block.
 std::vector<Fr> raw_trace_columns(const lsp_raw_trace& t, size_t height) {
-    std::vector<Fr> out;
-    auto put = [&](const std::vector<Fr>& c) {
+    const bool lookup = t.kind == LSP_AIR_LOOKUP;
+    std::vector<Fr> out((lookup ? t.lookup().raw_cols() : t.perm().raw_cols()) * height, fr_zero());
+    auto put = [&](size_t col, const std::vector<Fr>& c) {
         LSP_REQUIRE(c.size() <= height, LSP_E_ARG, "column longer than the requested height");
-        out.insert(out.end(), c.begin(), c.end());
-        out.resize(out.size() + (height - c.size()), fr_zero());
+        if (out.size() < (col + 1) * height) out.resize((col + 1) * height, fr_zero());
+        std::copy(c.begin(), c.end(), out.begin() + col * height);
     };
-    for (auto& c : t.a) put(c);
-    for (auto& c : t.b) put(c);
-    if (t.kind == LSP_AIR_LOOKUP) {
-        put(t.a_filter);
-        for (auto& f : t.b_filter) put(f);
+    const size_t raw_a = lookup ? t.lookup().raw_a() : t.perm().raw_a();
+    const size_t raw_b = lookup ? t.lookup().raw_b() : t.perm().raw_b();
+    for (size_t k = 0; k < t.a.size(); ++k) put(raw_a + k, t.a[k]);
+    for (size_t k = 0; k < t.b.size(); ++k) put(raw_b + k, t.b[k]);
+    if (lookup) {
+        put(t.lookup().raw_a_filter(), t.a_filter);
+        for (size_t k = 0; k < t.b_filter.size(); ++k) put(t.lookup().raw_b_filter() + k, t.b_filter[k]);
     }
     return out;
 }

@@ -393,6 +393,9 @@ struct lsp_raw_trace {
     uint32_t ntables = 0, nbc = 0;           // permutation: ntables = number of b columns
     std::vector<lsp::Fr> a_filter;
     std::vector<std::vector<lsp::Fr>> b_filter;
+    // its block's layout, by kind
+    lsp::PermBlock perm() const { return {(uint32_t)a.size(), (uint32_t)b.size()}; }
+    lsp::LookupBlock lookup() const { return {(uint32_t)a.size(), ntables, nbc}; }
 };
 
 // A committed batch: owns its device memory (freed on its context's device)

@@ -2,10 +2,12 @@
 // RawPermutationTrace::get_trace (trace/src/permutation.rs:24-93) and
 // RawLookupTrace::get_trace (trace/src/lookup.rs:46-176), writing the
 // columns straight into the row-major trace of RawTrace::get_trace
-// (trace/src/lib.rs:94-106).  Every kernel here is hand-written:
+// (trace/src/lib.rs:94-106).  Which column of a block holds what is
+// witness_layout.hpp's business: the row kernels take a PermBlock / LookupBlock
+// by value and ask it.  Every kernel here is hand-written:
 //
 //   rows         one thread per row: copy the raw columns into the trace row,
-//                Horner row combinations sum_j c_j alpha^(k-1-j)
+//                Horner row combinations sum_j c_j alpha^(k-1-j) (put_combo)
 //   inverses     launch_batch_inverse (k_field.hip)
 //   scans        the permutation check column is a prefix PRODUCT
 //                (trace/src/permutation.rs:72), the LogUp column a prefix SUM
@@ -124,67 +126,45 @@ __device__ __forceinline__ bool fr_nonzero(const Fr& x) {
     return o != 0;
 }
 
-__global__ __launch_bounds__(256) void k_perm_rows(const Fr* __restrict__ a, uint32_t na, const Fr* __restrict__ b,
-                                                   uint32_t nb, size_t n, Fr alpha, Fr delta, Fr* __restrict__ out,
-                                                   size_t ostride, Fr* __restrict__ al, Fr* __restrict__ bl,
+__global__ __launch_bounds__(256) void k_perm_rows(const Fr* __restrict__ a, const Fr* __restrict__ b, PermBlock blk,
+                                                   size_t n, Fr alpha, Fr delta, Fr* __restrict__ out, size_t ostride,
+                                                   Fr* __restrict__ al, Fr* __restrict__ bl,
                                                    uint32_t* __restrict__ zflag) {
     const size_t i = gtid();
     if (i >= n) return;
     Fr* row = out + i * ostride;
-    Fr acc = fr_zero();
-    for (uint32_t k = 0; k < na; ++k) {
-        const Fr v = a[k * n + i];
-        row[k] = v;
-        acc = fr_add(fr_mul(acc, alpha), v);
-    }
-    al[i] = fr_add(acc, delta);
-    acc = fr_zero();
-    for (uint32_t k = 0; k < nb; ++k) {
-        const Fr v = b[k * n + i];
-        row[na + k] = v;
-        acc = fr_add(fr_mul(acc, alpha), v);
-    }
-    const Fr d = fr_add(acc, delta);
+    al[i] = fr_add(put_combo(a, blk.na, n, i, alpha, row, [&](uint32_t k) { return blk.a(k); }), delta);
+    const Fr d = fr_add(put_combo(b, blk.nb, n, i, alpha, row, [&](uint32_t k) { return blk.b(k); }), delta);
     bl[i] = d;
     if (!fr_nonzero(d)) atomicOr(zflag, 1u);
 }
 
 // comb[0][i] = A row combination, comb[1+t][i] = table t's; den = comb + delta;
 // *zflag becomes nonzero if some den is 0 (a denominator the reference cannot invert)
-__global__ __launch_bounds__(256) void k_lookup_rows(const Fr* __restrict__ a, uint32_t na, const Fr* __restrict__ b,
-                                                     uint32_t nt, uint32_t nbc, const Fr* __restrict__ afil,
+__global__ __launch_bounds__(256) void k_lookup_rows(const Fr* __restrict__ a, const Fr* __restrict__ b,
+                                                     LookupBlock blk, const Fr* __restrict__ afil,
                                                      const Fr* __restrict__ bfil, size_t n, Fr alpha, Fr delta,
                                                      Fr* __restrict__ out, size_t ostride, Fr* __restrict__ comb,
                                                      Fr* __restrict__ den, uint32_t* __restrict__ zflag) {
     const size_t i = gtid();
     if (i >= n) return;
     Fr* row = out + i * ostride;
-    Fr acc = fr_zero();
-    for (uint32_t k = 0; k < na; ++k) {
-        const Fr v = a[k * n + i];
-        row[k] = v;
-        acc = fr_add(fr_mul(acc, alpha), v);
-    }
+    Fr acc = put_combo(a, blk.na, n, i, alpha, row, [&](uint32_t k) { return blk.a(k); });
     comb[i] = acc;
     Fr d = fr_add(acc, delta);
     den[i] = d;
     bool zero = !fr_nonzero(d);
-    for (uint32_t t = 0; t < nt; ++t) {
-        acc = fr_zero();
-        for (uint32_t k = 0; k < nbc; ++k) {
-            const Fr v = b[((size_t)t * nbc + k) * n + i];
-            row[na + t * nbc + k] = v;
-            acc = fr_add(fr_mul(acc, alpha), v);
-        }
+    for (uint32_t t = 0; t < blk.nt; ++t) {
+        acc = put_combo(b + (size_t)t * blk.nbc * n, blk.nbc, n, i, alpha, row,
+                        [&](uint32_t k) { return blk.b(t, k); });
         comb[(1 + (size_t)t) * n + i] = acc;
         d = fr_add(acc, delta);
         den[(1 + (size_t)t) * n + i] = d;
         zero |= !fr_nonzero(d);
     }
     if (zero) atomicOr(zflag, 1u);
-    const uint32_t f0 = na + nt * nbc;
-    row[f0] = afil[i];
-    for (uint32_t t = 0; t < nt; ++t) row[f0 + 1 + t] = bfil[(size_t)t * n + i];
+    row[blk.a_filter()] = afil[i];
+    for (uint32_t t = 0; t < blk.nt; ++t) row[blk.b_filter(t)] = bfil[(size_t)t * n + i];
 }
 
 // ---- LogUp occurrences: a device hash table over the row combinations.
@@ -263,20 +243,20 @@ __global__ __launch_bounds__(256) void k_occ_assign(const Fr* __restrict__ comb,
 // term[i] = [a_filter != 0] a_inv[i] - sum_t occ[t][i] b_inv[t][i]; writes the
 // a_inverses, b_inverses and multiplicities columns
 __global__ __launch_bounds__(256) void k_lookup_terms(const Fr* __restrict__ inv, const uint32_t* __restrict__ occ,
-                                                      const Fr* __restrict__ afil, size_t n, uint32_t nt,
-                                                      Fr* __restrict__ out, size_t ostride, uint32_t col_ainv,
+                                                      const Fr* __restrict__ afil, size_t n, LookupBlock blk,
+                                                      Fr* __restrict__ out, size_t ostride,
                                                       Fr* __restrict__ term) {
     const size_t i = gtid();
     if (i >= n) return;
     Fr* row = out + i * ostride;
     const Fr ai = inv[i];
-    row[col_ainv] = ai;
+    row[blk.a_inv()] = ai;
     Fr s = fr_nonzero(afil[i]) ? ai : fr_zero();
-    for (uint32_t t = 0; t < nt; ++t) {
+    for (uint32_t t = 0; t < blk.nt; ++t) {
         const Fr bi = inv[(1 + (size_t)t) * n + i];
         const Fr o = fr_from_u64(occ[(size_t)t * n + i]);
-        row[col_ainv + 1 + t] = bi;
-        row[col_ainv + 1 + nt + t] = o;
+        row[blk.b_inv(t)] = bi;
+        row[blk.mult(t)] = o;
         s = fr_sub(s, fr_mul(o, bi));
     }
     term[i] = s;
@@ -352,18 +332,18 @@ hipError_t launch_gen_raw_perm(uint64_t seed, size_t n, uint32_t ncols, uint64_t
     return hipGetLastError();
 }
 
-hipError_t launch_perm_rows(const Fr* a, uint32_t na, const Fr* b, uint32_t nb, size_t n, Fr alpha, Fr delta,
-                            Fr* out, size_t ostride, Fr* al, Fr* bl, uint32_t* zflag, hipStream_t st) {
-    hipLaunchKernelGGL(k_perm_rows, dim3(nblocks(n, 256)), dim3(256), 0, st, a, na, b, nb, n, alpha, delta, out,
-                       ostride, al, bl, zflag);
+hipError_t launch_perm_rows(const Fr* a, const Fr* b, PermBlock blk, size_t n, Fr alpha, Fr delta, Fr* out,
+                            size_t ostride, Fr* al, Fr* bl, uint32_t* zflag, hipStream_t st) {
+    hipLaunchKernelGGL(k_perm_rows, dim3(nblocks(n, 256)), dim3(256), 0, st, a, b, blk, n, alpha, delta, out, ostride,
+                       al, bl, zflag);
     return hipGetLastError();
 }
 
-hipError_t launch_lookup_rows(const Fr* a, uint32_t na, const Fr* b, uint32_t nt, uint32_t nbc, const Fr* afil,
-                              const Fr* bfil, size_t n, Fr alpha, Fr delta, Fr* out, size_t ostride, Fr* comb,
-                              Fr* den, uint32_t* zflag, hipStream_t st) {
-    hipLaunchKernelGGL(k_lookup_rows, dim3(nblocks(n, 256)), dim3(256), 0, st, a, na, b, nt, nbc, afil, bfil, n, alpha,
-                       delta, out, ostride, comb, den, zflag);
+hipError_t launch_lookup_rows(const Fr* a, const Fr* b, LookupBlock blk, const Fr* afil, const Fr* bfil, size_t n,
+                              Fr alpha, Fr delta, Fr* out, size_t ostride, Fr* comb, Fr* den, uint32_t* zflag,
+                              hipStream_t st) {
+    hipLaunchKernelGGL(k_lookup_rows, dim3(nblocks(n, 256)), dim3(256), 0, st, a, b, blk, afil, bfil, n, alpha, delta,
+                       out, ostride, comb, den, zflag);
     return hipGetLastError();
 }
 
@@ -410,10 +390,10 @@ hipError_t launch_lookup_occurrences(const Fr* comb, size_t n, uint32_t nt, cons
     return hipGetLastError();
 }
 
-hipError_t launch_lookup_terms(const Fr* inv, const uint32_t* occ, const Fr* afil, size_t n, uint32_t nt, Fr* out,
-                               size_t ostride, uint32_t col_ainv, Fr* term, hipStream_t st) {
-    hipLaunchKernelGGL(k_lookup_terms, dim3(nblocks(n, 256)), dim3(256), 0, st, inv, occ, afil, n, nt, out, ostride,
-                       col_ainv, term);
+hipError_t launch_lookup_terms(const Fr* inv, const uint32_t* occ, const Fr* afil, size_t n, LookupBlock blk, Fr* out,
+                               size_t ostride, Fr* term, hipStream_t st) {
+    hipLaunchKernelGGL(k_lookup_terms, dim3(nblocks(n, 256)), dim3(256), 0, st, inv, occ, afil, n, blk, out, ostride,
+                       term);
     return hipGetLastError();
 }
 

@@ -9,6 +9,7 @@
 #include "fr29.hpp"
 #include "ntt_plan.hpp"
 #include "poseidon2.hpp"
+#include "witness_layout.hpp"
 
 namespace lsp {
 
@@ -194,15 +195,30 @@ size_t witness_scratch_bytes(size_t n, uint32_t ntables);
 // hash values, b[c][i] = a[c][(mul i + add) mod n]; n a power of two, mul odd
 hipError_t launch_gen_raw_perm(uint64_t seed, size_t n, uint32_t ncols, uint64_t mul, uint64_t add, Fr* a, Fr* b,
                                hipStream_t st);
+// The columns of a block come from witness_layout.hpp (blk), relative to out.
+// The raw columns cols[k][i] (k < ncols, column-major over n rows) copied into
+// row i's cells col(k), and their Horner combination sum_k c_k alpha^(ncols-1-k):
+// the row kernels' and the host block functions' (witness.cpp) one loop
+template <class Col>
+LSP_HD Fr put_combo(const Fr* __restrict__ cols, uint32_t ncols, size_t n, size_t i, const Fr& alpha,
+                    Fr* __restrict__ row, Col col) {
+    Fr acc = fr_zero();
+    for (uint32_t k = 0; k < ncols; ++k) {
+        const Fr v = cols[k * n + i];
+        row[col(k)] = v;
+        acc = fr_add(fr_mul(acc, alpha), v);
+    }
+    return acc;
+}
 // trace row i (stride ostride): a cols, b cols; al/bl = row combination + delta.
 // *zflag (a device word the caller cleared) is set if some bl is 0
-hipError_t launch_perm_rows(const Fr* a, uint32_t na, const Fr* b, uint32_t nb, size_t n, Fr alpha, Fr delta,
-                            Fr* out, size_t ostride, Fr* al, Fr* bl, uint32_t* zflag, hipStream_t st);
+hipError_t launch_perm_rows(const Fr* a, const Fr* b, PermBlock blk, size_t n, Fr alpha, Fr delta, Fr* out,
+                            size_t ostride, Fr* al, Fr* bl, uint32_t* zflag, hipStream_t st);
 // trace row i: a cols, b tables, a_filter, b_filters; comb / den: (1 + nt) x n.
 // *zflag (a device word the caller cleared) is set if some den is 0
-hipError_t launch_lookup_rows(const Fr* a, uint32_t na, const Fr* b, uint32_t nt, uint32_t nbc, const Fr* afil,
-                              const Fr* bfil, size_t n, Fr alpha, Fr delta, Fr* out, size_t ostride, Fr* comb,
-                              Fr* den, uint32_t* zflag, hipStream_t st);
+hipError_t launch_lookup_rows(const Fr* a, const Fr* b, LookupBlock blk, const Fr* afil, const Fr* bfil, size_t n,
+                              Fr alpha, Fr delta, Fr* out, size_t ostride, Fr* comb, Fr* den, uint32_t* zflag,
+                              hipStream_t st);
 hipError_t launch_mul_vec(const Fr* x, const Fr* y, size_t n, Fr* out, hipStream_t st);
 hipError_t launch_put_col(const Fr* v, size_t n, Fr* out, size_t ostride, uint32_t col, hipStream_t st);
 // inclusive prefix product (product = true) or sum over Fr
@@ -211,9 +227,9 @@ hipError_t launch_fr_scan(const Fr* in, Fr* out, size_t n, bool product, void* s
 // LogUp multiplicities occ[t][i] (RawLookupTrace::get_trace's occurrence map)
 hipError_t launch_lookup_occurrences(const Fr* comb, size_t n, uint32_t nt, const Fr* afil, const Fr* bfil,
                                      uint32_t* occ, void* scratch, size_t scratch_bytes, hipStream_t st);
-// a_inverses / b_inverses / multiplicities columns from col_ainv on, and the LogUp terms
-hipError_t launch_lookup_terms(const Fr* inv, const uint32_t* occ, const Fr* afil, size_t n, uint32_t nt, Fr* out,
-                               size_t ostride, uint32_t col_ainv, Fr* term, hipStream_t st);
+// the a_inverse / b_inverse / multiplicity columns, and the LogUp terms
+hipError_t launch_lookup_terms(const Fr* inv, const uint32_t* occ, const Fr* afil, size_t n, LookupBlock blk, Fr* out,
+                               size_t ostride, Fr* term, hipStream_t st);
 
 // ----------------------------------------------------- k_quotient.hip
 struct QuotientArgs {

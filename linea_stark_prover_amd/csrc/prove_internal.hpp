@@ -400,13 +400,15 @@ lsp_proof* proof_from_view(const lsp_proof_view& v);
 Comm* make_callback_comm(const lsp_comm_ops& ops);
 void rccl_unique_id(uint8_t out[128]);
 Comm* make_rccl_comm(const uint8_t id[128], int rank, int size);
-// witness blocks on the device (witness.cpp): rows written at out + i * ostride
+// witness blocks on the device (witness.cpp): raw columns column-major in, rows
+// written at out + i * ostride in witness_layout.hpp's order
 void witness_permutation_device(lsp_ctx* ctx, const Fr* a, uint32_t na, const Fr* b, uint32_t nb, size_t n,
                                 const Fr& alpha, const Fr& delta, Fr* out, size_t ostride);
 void witness_lookup_device(lsp_ctx* ctx, const Fr* a, uint32_t na, const Fr* b, uint32_t nt, uint32_t nbc,
                            const Fr* afil, const Fr* bfil, size_t n, const Fr& alpha, const Fr& delta, Fr* out,
                            size_t ostride);
-// CBOR RawPermutationTrace / RawLookupTrace (cbor.cpp)
+// CBOR RawPermutationTrace / RawLookupTrace (cbor.cpp).  raw_trace_columns: the
+// columns resized to `height`, column-major in the block's raw order
 lsp_raw_trace* parse_raw_trace(const uint8_t* buf, size_t len);
 void raw_trace_shape(const lsp_raw_trace& t, size_t& height, size_t& width);
 std::vector<Fr> raw_trace_columns(const lsp_raw_trace& t, size_t height);

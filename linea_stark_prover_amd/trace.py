@@ -72,7 +72,7 @@ class RawPermutationTrace:
         return max(len(c) for c in list(self.a) + list(self.b))
 
     def width(self) -> int:
-        return len(self.a) + len(self.b) + 2
+        return AirPermutationConfig.block(len(self.a), len(self.b)).width()
 
 
 @dataclass
@@ -117,7 +117,7 @@ class RawLookupTrace:
         return max([len(c) for c in self.a] + [len(c) for t in self.b for c in t])
 
     def width(self) -> int:
-        return len(self.a) + len(self.b) * (len(self.b[0]) + 3) + 3
+        return AirLookupConfig.block(len(self.a), len(self.b), len(self.b[0])).width()
 
 
 class RawTrace:
@@ -177,9 +177,7 @@ class RawTrace:
         self.ctx._chk(L.lib().lsp_witness_permutation(
             self.ctx.h, da, na, db, nb, n, _ptr(self.alpha), _ptr(self.delta), self.ptr, self.width, col0,
             L.LSP_MEM_DEVICE))
-        cfg = AirPermutationConfig(list(range(na)), list(range(na, na + nb)), na + nb, na + nb + 1)
-        cfg.shift(col0)
-        return cfg
+        return AirPermutationConfig.block(na, nb, col0)
 
     def _push_lookup(self, lt: RawLookupTrace, col0: int) -> AirLookupConfig:
         n = self.height
@@ -193,17 +191,7 @@ class RawTrace:
         self.ctx._chk(L.lib().lsp_witness_lookup(
             self.ctx.h, ptrs[0], na, ptrs[1], nt, nbc, ptrs[2], ptrs[3], n, _ptr(self.alpha),
             _ptr(self.delta), self.ptr, self.width, col0, L.LSP_MEM_DEVICE))
-        # column ids (trace/src/lookup.rs:178-214)
-        a_ids = list(range(na))
-        b_ids = [[na + t * nbc + c for c in range(nbc)] for t in range(nt)]
-        af_id = na + nt * nbc
-        bf_ids = [af_id + 1 + t for t in range(nt)]
-        ai_id = af_id + 1 + nt
-        bi_ids = [ai_id + 1 + t for t in range(nt)]
-        oc_ids = [ai_id + 1 + nt + t for t in range(nt)]
-        cfg = AirLookupConfig(a_ids, b_ids, af_id, bf_ids, ai_id, bi_ids, oc_ids, ai_id + 1 + 2 * nt)
-        cfg.shift(col0)
-        return cfg
+        return AirLookupConfig.block(na, nt, nbc, col0)
 
     def _upload_cols(self, cols, n: int, p: int) -> int:
         """len(cols) columns of n elements each, column-major at device address

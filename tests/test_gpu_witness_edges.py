@@ -318,6 +318,61 @@ def test_uneven_column_counts_in_a_wider_trace(wit_ctx, kind, name, mem):
     assert np.array_equal(got, before)
 
 
+# ------------------------------------------- CBOR raw traces into a wider trace
+def _padded(kind, name):
+    """(the case's CBOR bytes, the reference's columns of the case resized with
+    zero words to PAD_ROWS rows above its longest column)"""
+    golden = os.path.join(HERE, "golden")
+    if golden not in sys.path:
+        sys.path.insert(0, golden)
+    import cbor_enc as C
+    if kind == "permutation":
+        return C.enc(C.permutation_trace(*W.PERM_CASES[name]())), row_major(W.padded_perm_columns(name))
+    return C.enc(C.lookup_trace(*W.LOOKUP_CASES[name]())), row_major(W.padded_lookup_columns(name))
+
+
+@pytest.mark.parametrize("mem", [HOST, DEVICE], ids=["host", "device"])
+@pytest.mark.parametrize("kind,name", UNEVEN, ids=[f"{k}-{n}" for k, n in UNEVEN])
+def test_raw_trace_push_into_a_wider_trace(wit_ctx, kind, name, mem):
+    """lsp_raw_trace_push carves a (na != nb), (a, b, a_filter, b_filter with na
+    != nbc, one and two tables) out of one column-major block of the parsed
+    CBOR trace.  Height = longest column + 3 (12 or 14 rows), so the columns
+    are resized with zero words and every carved pointer differs from its
+    neighbours by a column count times the height; the block goes to columns
+    2 .. 2 + width - 1 of a trace three columns wider, in host and in device
+    memory.  Inside the block: the reference's witness of the zero-padded
+    columns (tests/test_witness_cases.py: the reference accepts all four padded
+    cases, so none runs at height = longest column); outside: untouched."""
+    import ctypes
+    from linea_stark_prover_amd import _lib as L
+    cbor, exp = _padded(kind, name)
+    n, bw = exp.shape[0], exp.shape[1]
+    col0, before = 2, sentinel(n, bw + 3)
+    al, de = challenge_words()
+    got = before.copy()
+    h = ctypes.c_void_p()
+    L.check(L.lib().lsp_raw_trace_parse(cbor, len(cbor), ctypes.byref(h)))
+    dev = None
+    try:
+        mh, w = ctypes.c_size_t(), ctypes.c_size_t()
+        L.check(L.lib().lsp_raw_trace_shape(h, None, None, None, None, ctypes.byref(mh), ctypes.byref(w)))
+        assert (mh.value, w.value) == (n - W.PAD_ROWS, bw)
+        tptr = got.ctypes.data
+        if mem == DEVICE:
+            dev = tptr = wit_ctx.dev_alloc(got.nbytes)
+            wit_ctx.h2d(dev, got)
+        rc = L.lib().lsp_raw_trace_push(wit_ctx.h, h, n, al.ctypes.data, de.ctypes.data, tptr, got.shape[1], col0, mem)
+        assert rc == L.LSP_OK, (rc, L.lib().lsp_last_error(wit_ctx.h))
+        if mem == DEVICE:
+            wit_ctx.d2h(got, dev)
+    finally:
+        L.lib().lsp_raw_trace_free(h)
+        if dev is not None:
+            wit_ctx.dev_free(dev)
+    assert np.array_equal(got[:, col0:col0 + bw], exp), _first_difference(got[:, col0:col0 + bw], exp)
+    assert np.array_equal(got[:, :col0], before[:, :col0]) and np.array_equal(got[:, col0 + bw:], before[:, col0 + bw:])
+
+
 # --------------------------------------------------------------- generator
 def _generated(ctx, log_n, ncols, seed):
     al, de = challenge_words()

@@ -22,6 +22,27 @@ def test_wide_trace_matches_pyoracle(product_lib, log_n, shape):
     assert air.descriptor() == cref.air_desc(cfgs)
 
 
+@pytest.mark.parametrize("log_n,shape", [(3, (1, 2, 2, 1, 2)), (4, (2, 3, 2, 2, 3)), (5, (1, 3, 3, 0, 1)),
+                                         (3, (4, 3, 2, 8, 6))], ids=["3", "4", "5", "default"])
+def test_block_constructors_give_the_generators_descriptor(product_lib, log_n, shape):
+    """AirLookupConfig.block / AirPermutationConfig.block, lookups first at
+    running col0, are the descriptor the C generator writes (witness_layout.hpp's describe)"""
+    from linea_stark_prover_amd.air import AirLookupConfig, AirPermutationConfig, LineaAIR
+    from linea_stark_prover_amd.prover import StarkConfig, gen_wide_trace
+    nlookup, na, ntab, nperm, pcols = shape
+    a, d, _ = StarkConfig().seeded()
+    args = () if shape == (4, 3, 2, 8, 6) else shape  # the default shape by default
+    tr, air = gen_wide_trace(log_n, a, d, *args)
+    cfgs, col0 = [], 0
+    for _ in range(nlookup):
+        cfgs.append(AirLookupConfig.block(na, ntab, na, col0))
+        col0 += cfgs[-1].width()
+    for _ in range(nperm):
+        cfgs.append(AirPermutationConfig.block(pcols, pcols, col0))
+        col0 += cfgs[-1].width()
+    assert LineaAIR(cfgs).descriptor() == air.descriptor() and col0 == tr.shape[1]
+
+
 def test_wide_trace_default_width(product_lib):
     from linea_stark_prover_amd.prover import StarkConfig, gen_wide_trace
     a, d, _ = StarkConfig().seeded()

@@ -136,6 +136,31 @@ def test_reference_on_permutation_case(name):
     assert len(cols) == len(a) + len(b) + 2 and cols[-1][-1] == 1
 
 
+@pytest.mark.parametrize("name", sorted(W.PERM_CASES))
+def test_reference_on_padded_permutation_case(name):
+    """the reference accepts the case resized with zero words to PAD_ROWS rows
+    above its longest column, and its first rows are the unpadded case's"""
+    a, b = W.padded_perm_case(name)
+    n = len(W.PERM_CASES[name]()[0][0])
+    assert all(len(c) == n + W.PAD_ROWS and c[n:] == [0] * W.PAD_ROWS for c in a + b)
+    cols = W.padded_perm_columns(name)
+    assert len(cols) == len(a) + len(b) + 2 and cols[-1][-1] == 1
+    assert [c[:n] for c in cols] == W.perm_columns(name)
+
+
+@pytest.mark.parametrize("name", W.LOOKUP_UNEVEN)
+def test_reference_on_padded_lookup_case(name):
+    """as above for the lookups: the padded rows are disabled (zero filters),
+    so the multiplicities and the sum's end stay"""
+    a, b, af, bf = W.padded_lookup_case(name)
+    n = len(W.LOOKUP_CASES[name]()[0][0])
+    assert all(len(c) == n + W.PAD_ROWS and c[n:] == [0] * W.PAD_ROWS for c in a + [c for t in b for c in t] + [af] + bf)
+    cols = W.padded_lookup_columns(name)
+    assert cols[-1][-1] == 0 and [c[:n] for c in cols] == W.lookup_columns(name)
+    assert len(a) != len(b[0])  # na != nbc
+    assert max(len(W.LOOKUP_CASES[k]()[1]) for k in W.LOOKUP_UNEVEN) == 2  # one of them has two tables
+
+
 @pytest.mark.parametrize("n", W.PERM_SCAN_SIZES)
 def test_reference_on_permutation_scan_shape(n):
     assert W.rotation_perm_columns(n)[3][-1] == 1

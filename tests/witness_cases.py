@@ -207,7 +207,7 @@ def gen_value(seed, c, i):
 
 
 def gen_row_map(seed, log_n):
-    """(mul, add) of lsp_gen_permutation_trace_device (capi.cpp): B's row i is
+    """(mul, add) of lsp_gen_permutation_trace_device (witness.cpp): B's row i is
     A's row (mul i + add) mod 2^log_n, mul odd"""
     mul = (((seed * 0xD1B54A32D192ED03) & M64) ^ 0x5851F42D4C957F2D) | 1
     add = (seed * 0xA24BAED4963EE407 + 0x9FB21C651E98DF25) & M64
@@ -397,6 +397,39 @@ def lookup_columns(name):
 @functools.lru_cache(maxsize=None)
 def perm_columns(name):
     return O.perm_witness(*PERM_CASES[name](), *challenges())[1]
+
+
+# The uneven cases as lsp_raw_trace_push sees them at a height above their
+# longest column: every raw column, the filters too, resized with zero words
+# (RawTrace's Vec::resize).  A padded row adds delta / delta to the product
+# and, its filters being 0, nothing to the sum.
+PAD_ROWS = 3
+
+
+def _padded(cols, h):
+    return [list(c) + [0] * (h - len(c)) for c in cols]
+
+
+def padded_perm_case(name):
+    a, b = PERM_CASES[name]()
+    h = max(len(c) for c in a + b) + PAD_ROWS
+    return _padded(a, h), _padded(b, h)
+
+
+def padded_lookup_case(name):
+    a, b, af, bf = LOOKUP_CASES[name]()
+    h = max(len(c) for c in a + [c for t in b for c in t]) + PAD_ROWS
+    return _padded(a, h), [_padded(t, h) for t in b], _padded([af], h)[0], _padded(bf, h)
+
+
+@functools.lru_cache(maxsize=None)
+def padded_perm_columns(name):
+    return O.perm_witness(*padded_perm_case(name), *challenges())[1]
+
+
+@functools.lru_cache(maxsize=None)
+def padded_lookup_columns(name):
+    return O.lookup_witness(*padded_lookup_case(name), *challenges())[1]
 
 
 @functools.lru_cache(maxsize=None)
