@@ -113,7 +113,20 @@ typedef struct lsp_proof lsp_proof;
  * bytes on LP64 for this layout): lsp_ctx_create rejects any other
  * value with LSP_E_ARG, so a caller built against an older layout (whose
  * first field was sbox_degree = 11 or 17) fails loudly instead of having
- * its stack read as the newer fields. */
+ * its stack read as the newer fields.
+ *
+ * Admitted domain (anything else: LSP_E_ARG from lsp_ctx_create):
+ *   sbox_degree 11 or 17; rounds_f 2..64, even; rounds_p 0..256;
+ *   log_blowup 1..8; log_final_poly_len 0..8; num_queries 1..1024;
+ *   proof_of_work_bits 0..32; public_degree 0 or 1; the switches 0 or 1.
+ * The height rule: a trace of h rows is proved and verified only when
+ * log2(h) > log_final_poly_len, i.e. FRI has at least one commit-phase round
+ * (the verifier's fold chain takes the reduced opening in at its first round;
+ * with none, no proof can be accepted).  lsp_prove, lsp_prove_preprocessed,
+ * lsp_prove_group and lsp_prove_sharded answer LSP_E_SIZE ("an LDE height
+ * below 2 * 2^(log_blowup + log_final_poly_len)", as the PCS entry points);
+ * lsp_verify rejects such a header.  The AIR adds: log_quotient_degree <=
+ * log_blowup (LSP_E_ARG, "quotient degree exceeds the blowup"). */
 typedef struct {
     uint32_t struct_size;          /* sizeof(lsp_params) */
     uint32_t sbox_degree;          /* U1: 11 (default) or 17 */

@@ -194,6 +194,11 @@ Shard shard_geometry(const lsp_ctx* ctx, const Comm& comm, size_t h, size_t w, c
     s.log_h = log2_exact(h);
     LSP_REQUIRE(h >= 2, LSP_E_SIZE, "trace needs at least 2 rows");
     s.lb = ctx->log_blowup;
+    // log2(h) <= log_final_poly_len leaves FRI no commit-phase round, and the
+    // verifier's fold chain has no round that could take the reduced opening in
+    // (fri_check_query; pcs.cpp refuses the same shape)
+    LSP_REQUIRE(s.log_h > ctx->log_final_poly_len, LSP_E_SIZE,
+                "an LDE height below 2 * 2^(log_blowup + log_final_poly_len)");
     s.log_q = air.log_quotient_degree(ctx->public_degree);
     LSP_REQUIRE(s.log_q <= s.lb, LSP_E_ARG, "quotient degree exceeds the blowup");
     s.q = (size_t)1 << s.log_q;

@@ -41,6 +41,9 @@ int verify_host(const lsp_ctx* ctx, const Air& air, const Fr* pub, size_t npub, 
         log_h < 1 || w <= air.max_col || w > (1u << 20) || air.max_pub >= (int64_t)npub)
         return 3;
     const uint32_t lb = ctx->log_blowup, logN = log_h + lb;
+    // a proof without a commit-phase round is never valid: the fold chain of a
+    // query starts from zero and takes the reduced opening in at its first round
+    if (log_h <= ctx->log_final_poly_len) return 4;
     if (nr != logN - lb - ctx->log_final_poly_len || nf != (1u << ctx->log_final_poly_len)) return 4;
     const size_t q = (size_t)1 << log_q, h = (size_t)1 << log_h;
     const size_t flen = (size_t)1 << ctx->log_final_poly_len;

@@ -53,6 +53,7 @@ def lib():
         if not os.path.exists(LIB_PATH):
             build()
         L = ctypes.CDLL(LIB_PATH)
+        L.lo_setup.restype = ctypes.c_int
         L.lo_prove.restype = ctypes.c_int
         L.lo_verify.restype = ctypes.c_int
         L.lo_log_quotient_degree.restype = ctypes.c_int
@@ -135,7 +136,9 @@ def set_linear_layers(p: Params, int_diag=None, ext_mds=None) -> Params:
 def setup(seed: int = O.DEFAULT_SEED, sbox_degree=11, rounds_f=8, rounds_p=22, int_diag=None,
           ext_mds=None) -> Params:
     p = Params()
-    lib().lo_setup(ctypes.c_uint64(seed), sbox_degree, rounds_f, rounds_p, ctypes.byref(p))
+    rc = lib().lo_setup(ctypes.c_uint64(seed), sbox_degree, rounds_f, rounds_p, ctypes.byref(p))
+    if rc != 0:
+        raise ValueError(f"lo_setup: round counts ({rounds_f}, {rounds_p}) beyond the C oracle's capacity (16, 64)")
     return set_linear_layers(p, int_diag, ext_mds)
 
 

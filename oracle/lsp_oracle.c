@@ -322,9 +322,16 @@ static uint64_t smix_below(smix *r, uint64_t n) {
     }
 }
 
-void lo_setup(uint64_t seed, uint32_t sbox_degree, uint32_t rounds_f, uint32_t rounds_p, lo_params *out) {
+/* the round counts lo_params has room for (the product context admits up to
+ * 64 full and 256 partial rounds: beyond these the oracle is no reference) */
+static int rounds_fit(uint32_t rounds_f, uint32_t rounds_p) {
+    return rounds_f / 2 <= LO_MAX_HALF_ROUNDS_F && rounds_p <= LO_MAX_ROUNDS_P;
+}
+
+int lo_setup(uint64_t seed, uint32_t sbox_degree, uint32_t rounds_f, uint32_t rounds_p, lo_params *out) {
     field_init();
     memset(out, 0, sizeof *out);
+    if (!rounds_fit(rounds_f, rounds_p)) return -1;
     smix r = {seed};
     out->sbox_degree = sbox_degree;
     out->rounds_f = rounds_f;
@@ -336,6 +343,7 @@ void lo_setup(uint64_t seed, uint32_t sbox_degree, uint32_t rounds_f, uint32_t r
     for (uint32_t i = 0; i < rounds_f / 2; ++i)
         for (int j = 0; j < 3; ++j) out->ext_terminal[i][j] = smix_fr(&r);
     for (uint32_t i = 0; i < rounds_p; ++i) out->internal[i] = smix_fr(&r);
+    return 0;
 }
 
 /* -------------------------------------------------------------- Poseidon2 */
@@ -1054,8 +1062,12 @@ int lo_prove(const lo_params *p, const lo_fri *fri, const lo_fr *trace, size_t h
     static cfg_t cfgs[MAXCFG];
     int ncfg, K;
     if (parse_air(air, air_len, cfgs, &ncfg)) return -1;
+    if (!rounds_fit(p->rounds_f, p->rounds_p)) return -4;
     uint32_t log_h = log2_strict(h);
     if (log_h == 0xFFFFFFFFu || h < 2) return -2;
+    /* no commit-phase round: the verifier's fold chain would start and end at
+     * zero, so no such proof is ever accepted (the product refuses the shape) */
+    if (log_h <= fri->log_final_poly_len) return -5;
     int maxd = constraint_stats(cfgs, ncfg, public_degree, &K);
     if (maxd < 2) maxd = 2;
     uint32_t log_q = 0;
@@ -1342,6 +1354,7 @@ int lo_verify(const lo_params *p, const lo_fri *fri, const int32_t *air, size_t 
     static cfg_t cfgs[MAXCFG];
     int ncfg, K;
     if (parse_air(air, air_len, cfgs, &ncfg)) return -1;
+    if (!rounds_fit(p->rounds_f, p->rounds_p)) return -4;
     rd_t r = {proof, proof_len, 0, 0};
     if (proof_len < 8 || memcmp(proof, "LSPPRF02", 8)) return 1;
     r.off = 8;

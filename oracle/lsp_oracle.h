@@ -25,11 +25,13 @@ extern "C" {
 
 typedef struct { uint64_t l[4]; } lo_fr;
 
+enum { LO_MAX_HALF_ROUNDS_F = 8, LO_MAX_ROUNDS_P = 64 }; /* capacity: rounds_f <= 16, rounds_p <= 64 */
+
 typedef struct {
     uint32_t sbox_degree, rounds_f, rounds_p;
-    lo_fr ext_initial[8][3];
-    lo_fr ext_terminal[8][3];
-    lo_fr internal[64];
+    lo_fr ext_initial[LO_MAX_HALF_ROUNDS_F][3];
+    lo_fr ext_terminal[LO_MAX_HALF_ROUNDS_F][3];
+    lo_fr internal[LO_MAX_ROUNDS_P];
     lo_fr alpha, delta; /* permutation challenges (public values) */
     /* U2/U3 linear layers: generic_lin == 0 -> the defaults (external
      * circ(2,1,1), internal J + diag(1,1,2)); otherwise s <- ext_mds s
@@ -62,8 +64,9 @@ void lo_fr_mul(const lo_fr *a, const lo_fr *b, lo_fr *out);
 void lo_fr_add(const lo_fr *a, const lo_fr *b, lo_fr *out);
 void lo_fr_inv(const lo_fr *a, lo_fr *out);
 
-/* U4/U5 seeded setup (SplitMix64): alpha, delta, then Poseidon2 constants */
-void lo_setup(uint64_t seed, uint32_t sbox_degree, uint32_t rounds_f, uint32_t rounds_p, lo_params *out);
+/* U4/U5 seeded setup (SplitMix64): alpha, delta, then Poseidon2 constants.
+ * Nonzero (and *out zeroed) for round counts beyond lo_params' capacity. */
+int lo_setup(uint64_t seed, uint32_t sbox_degree, uint32_t rounds_f, uint32_t rounds_p, lo_params *out);
 
 /* primitives */
 void lo_poseidon2_permute(const lo_params *p, lo_fr state[3]);
@@ -89,7 +92,10 @@ int lo_gen_perm_trace(uint32_t log_n, uint32_t ncols, const lo_fr *alpha, const 
 int lo_log_quotient_degree(const int32_t *air, size_t air_len, int public_degree);
 
 /* Full prove. proof bytes are malloc'd; free with lo_free. dbg (nullable)
- * receives intermediate vectors for parity tests: see lsp_oracle.c. */
+ * receives intermediate vectors for parity tests: see lsp_oracle.c.
+ * Errors: -1 AIR descriptor, -2 height, -3 quotient degree above the blowup,
+ * -4 round counts beyond lo_params' capacity, -5 log2(h) <= log_final_poly_len
+ * (FRI would have no commit-phase round; no verifier accepts such a proof). */
 typedef struct {
     lo_fr *trace_lde;       /* N*w */
     lo_fr *trace_layers;    /* 2N-1 */

@@ -796,6 +796,9 @@ def prove(cfgs, trace_rows: List[List[int]], pub: List[int], pp: Poseidon2Params
     log_h = log2_strict(h)
     w = len(trace_rows[0])
     lb = fri.log_blowup
+    # the height rule (include/lsp.h lsp_params): without a commit-phase round the
+    # verifier's fold chain never takes the reduced opening in, so no proof verifies
+    assert log_h > fri.log_final_poly_len, "log2(h) must exceed log_final_poly_len: FRI needs a round"
     log_q = log_quotient_degree(cfgs, public_degree)
     q = 1 << log_q
     nconstraints = len(constraint_degrees(cfgs, public_degree))
